@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Headline benchmark: TeraSort shuffle+merge GB/s, whole node (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON result line; everything else the
+benchmark can check is behind --full (below).
 
 One process per GPU. Under torchrun (RANK/LOCAL_RANK/WORLD_SIZE set) this process is one rank;
 otherwise `--gpus N` (N > 1) starts the N rank processes itself (before anything touches the GPU)
@@ -16,9 +19,16 @@ by their VInt lengths (J2CQueue); every step checks the parsed record count of e
 Per-GPU data is fixed (weak scaling): --rows-per-gpu TeraGen rows (104-byte IFile records) per
 GPU; the default 1.25e9 rows/GPU makes N=8 the 1 TB TeraSort config (N=1 moves 130 GB).
 
-After the timed steps one more (untimed) step runs with the device-side validation on: key order
-per reducer, record checksum against the generated data, and (N > 1) per-slice checksums of what
-every peer sent. "validated": true means that step passed.
+With --full one more (untimed) step runs after the timed steps with the device-side validation on:
+key order per reducer, record checksum against the generated data, and (N > 1) per-slice checksums
+of what every peer sent. "validated": true means that step passed; without --full it is null.
+
+--dump-outputs DIR writes what the consumers received in the last timed step as .npy files:
+`records.npy` (float32), a fixed sample of whole merged records of every reducer's stream (the record
+numbers are drawn once from the job's seed, the first and last record of every reducer among them;
+one row per record, one column per byte), `record_index.npy` (float64: reducer, record number of
+every row) and `reducer_records.npy` (float64: records every consumer parsed). The generated data depends on the arguments
+alone, so two builds run with the same arguments can be compared file by file.
 
 value = total partition bytes delivered on all GPUs / time per step (GB = 1e9 bytes).
 Data is synthetic (TeraGen-shaped keys/values generated in HBM; see uda_amd/models/terasort.py).
@@ -82,7 +92,13 @@ def parse_args(argv=None):
                     help="bound the HBM staging per round (raises --rounds so a round is at most this size)")
     ap.add_argument("--device-only", action="store_true",
                     help="ablation: stop after the device merge (no host delivery); not the headline")
-    ap.add_argument("--no-validate", action="store_true", help="skip the final validated step")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the validated step after the timed "
+                         "steps (every path: flagship, --api, --node)")
+    ap.add_argument("--no-validate", action="store_true", help="--full: skip the final validated step")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="flagship path: write a fixed sample of the records the consumers received in the last "
+                         "timed step, and their per-reducer counts, as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--sink", choices=("j2c", "none"), default="j2c",
                     help="ablation: 'none' drops delivered buffers unread (measures the copy path alone)")
     ap.add_argument("--api", action="store_true",
@@ -123,7 +139,9 @@ def parse_args(argv=None):
                          "box allows 16 GPU processes, the provider is one of them")
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--launch-selftest", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    args.validate = args.full and not args.no_validate
+    return args
 
 
 def free_port() -> int:
@@ -165,6 +183,10 @@ def launch_ranks(n: int, argv: list[str]) -> int:
 def main(argv=None) -> int:
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
+    if args.dump_outputs and (args.api or args.device_only or args.sink == "none"):
+        print("bench: --dump-outputs writes what the flagship path's consumers receive (not with --api, "
+              "--device-only or --sink none)", file=sys.stderr)
+        return 2
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus, argv)
     if args.launch_selftest:  # launcher check (CPU tests): report the rank environment, touch no GPU
@@ -209,6 +231,8 @@ def main(argv=None) -> int:
     job.setup()
     if args.sink == "none":
         job.drop_sink()
+    if args.dump_outputs:
+        job.sample_outputs(DUMP_RECORDS // max(1, args.reducers), seed=cfg.seed)
     t_setup = time.perf_counter() - t_setup
     if ctx.rank == 0:
         print(f"# setup {t_setup:.1f}s cpus={len(os.sched_getaffinity(0))} {job.setup_s} "
@@ -236,10 +260,12 @@ def main(argv=None) -> int:
     elapsed = ctx.max_float(elapsed)
     for st in stats:
         job.check(st)  # consumer record counts / framing / EOF of every timed step
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx.rank, job, stats[-1])
 
     validated = None
     exchange_errors = None
-    if not args.no_validate:
+    if args.validate:
         vst = job.step(validate=True)
         job.check(vst)  # raises on order / checksum / exchange-checksum errors
         ok = ctx.all_gather_object(int(vst["exchange_errors"]))
@@ -319,6 +345,24 @@ def main(argv=None) -> int:
         print(json.dumps(out), flush=True)
     ctx.close()
     return 0
+
+
+DUMP_RECORDS = 65536  # --dump-outputs: sampled records per GPU (104 float32 columns each: 27 MB)
+
+
+def dump_outputs(path: str, rank: int, job, last: dict) -> None:
+    """Write the sample of the last timed step's delivered records (job.sample_outputs) and the record
+    counts its consumers parsed as float32 .npy files; ranks other than 0 add `.rank<r>` to the names."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    tag = f".rank{rank}" if rank else ""
+    rows = job.sampled_outputs()
+    index = [np.stack([np.full(len(i), r, np.int64), i], axis=1) for r, i in enumerate(job.sample_index)]
+    np.save(os.path.join(path, f"records{tag}.npy"), np.concatenate(rows).astype(np.float32))
+    # float64: record numbers of a 130 GB job do not fit float32's 24 bits
+    np.save(os.path.join(path, f"record_index{tag}.npy"), np.concatenate(index).astype(np.float64))
+    np.save(os.path.join(path, f"reducer_records{tag}.npy"), np.asarray(last["consumer_records"], np.float64))
 
 
 RANK_DETAIL_KEYS = {"rank": int, "device": int, "numa_node": int, "consumer_cpus": str, "delivery": str,
@@ -563,7 +607,7 @@ def _run_waves(args, port, cmds, expected, exe, errlog, conf, sp, statistics):
             print(f"# warmup {i}: {json.dumps(warm[-1])}", file=sys.stderr, flush=True)
     stats = [wave(False) for _ in range(args.steps)]
     validated = None
-    if not args.no_validate:
+    if args.validate:
         validated = wave(True)["order_errors"] == 0
     return warm, stats, validated
 
@@ -794,7 +838,7 @@ def run_api(args, ctx) -> int:
     ctx.barrier()
     elapsed = ctx.max_float(time.perf_counter() - t0)
     validated = None
-    if not args.no_validate:
+    if args.validate:
         vst = b.step(True)
         validated = all(ctx.all_gather_object(vst["order_errors"] == 0))
         if args.verbose and rank == 0:

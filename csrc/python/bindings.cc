@@ -26,6 +26,7 @@
 #include "api_bench.h"
 #include "generic_merger.h"
 #include "j2c_sink.h"
+#include "stream_sampler.h"
 #include "uda/aio.h"
 #include "uda/codec.h"
 #include "uda/datagen.h"
@@ -1393,6 +1394,28 @@ PYBIND11_MODULE(_uda_native, m) {
         return rc;
       }, py::arg("reducer"), py::arg("data"), py::arg("reps") = 1);
 
+  // fixed windows of every reducer's delivered stream, kept beside the J2C sink (set_j2c_sink)
+  py::class_<gpu::StreamSampler, std::shared_ptr<gpu::StreamSampler>>(m, "StreamSampler")
+      .def(py::init<std::vector<std::vector<int64_t>>, int64_t>(), py::arg("starts"), py::arg("window"))
+      .def_property_readonly("reducers", &gpu::StreamSampler::reducers)
+      .def_property_readonly("window", &gpu::StreamSampler::window)
+      .def("reset", &gpu::StreamSampler::reset)
+      .def("observe", [](gpu::StreamSampler& s, int r, py::buffer b) {
+        py::buffer_info bi = b.request();
+        if (r < 0 || r >= s.reducers()) throw py::index_error("reducer out of range");
+        s.observe(r, static_cast<const uint8_t*>(bi.ptr), (int64_t)(bi.size * bi.itemsize));
+      }, py::arg("reducer"), py::arg("data"))
+      .def("stream_bytes", &gpu::StreamSampler::stream_bytes)
+      .def("captured_bytes", &gpu::StreamSampler::captured_bytes)
+      // reducer r's windows as a (windows, window) uint8 array (a copy)
+      .def("data", [](gpu::StreamSampler& s, int r) {
+        if (r < 0 || r >= s.reducers()) throw py::index_error("reducer out of range");
+        py::array_t<uint8_t> a({(py::ssize_t)s.windows(r), (py::ssize_t)s.window()});
+        const auto& d = s.data(r);
+        if (!d.empty()) std::memcpy(a.mutable_data(), d.data(), d.size());
+        return a;
+      });
+
   py::class_<gpu::ApiTeraSortBench>(m, "ApiTeraSortBench")
       .def(py::init([](const py::dict& d) {
         gpu::ApiBenchConfig c;
@@ -1474,10 +1497,19 @@ PYBIND11_MODULE(_uda_native, m) {
            })
       .def("plan", &gpu::ShuffleJob::plan, py::call_guard<py::gil_scoped_release>())
       .def("set_j2c_sink",
-           [](gpu::ShuffleJob& j, std::shared_ptr<gpu::J2CSink> s) {
+           [](gpu::ShuffleJob& j, std::shared_ptr<gpu::J2CSink> s, std::shared_ptr<gpu::StreamSampler> sampler) {
              if (s->reducers() != j.config().reducers) throw py::value_error("J2CSink reducer count mismatch");
-             j.set_sink([s](int r, const uint8_t* buf, int64_t len) { return s->consume(r, buf, len); });
-           })
+             if (!sampler) {
+               j.set_sink([s](int r, const uint8_t* buf, int64_t len) { return s->consume(r, buf, len); });
+               return;
+             }
+             if (sampler->reducers() != s->reducers()) throw py::value_error("StreamSampler reducer count mismatch");
+             j.set_sink([s, sampler](int r, const uint8_t* buf, int64_t len) {
+               sampler->observe(r, buf, len);
+               return s->consume(r, buf, len);
+             });
+           },
+           py::arg("sink"), py::arg("sampler") = std::shared_ptr<gpu::StreamSampler>())
       .def("set_python_sink",
            [](gpu::ShuffleJob& j, py::function fn, bool with_reducer) {
              auto holder = std::make_shared<py::function>(fn);

@@ -27,6 +27,17 @@ def native():
     return uda_amd.native()
 
 
+@pytest.fixture
+def sock_dir():
+    """A short directory for Unix socket files: sockaddr_un.sun_path holds 107 bytes, and pytest's
+    tmp_path under a deep TMPDIR is longer than that."""
+    import shutil
+    import tempfile
+    d = tempfile.mkdtemp(prefix="uda-", dir="/tmp")
+    yield d
+    shutil.rmtree(d, ignore_errors=True)
+
+
 @pytest.fixture(scope="session")
 def require_gpu():
     if not gpu_available():

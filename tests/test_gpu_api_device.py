@@ -205,7 +205,7 @@ def test_api_bench_two_ranks_share_providers(require_gpu):
     other rank's HBM mapped over hipIpc). Every task's record count is checked against the sum over
     both ranks' maps, key order in the validated step."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--api", "--gpus", "2", "--one-gpu",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--api", "--gpus", "2", "--one-gpu",
                           "--steps", "1", "--warmup", "1", "--rows-per-gpu", "1800000", "--maps-per-gpu", "6",
                           "--reducers", "3", "--round-mb", "16"],
                          capture_output=True, text=True, timeout=110, env=env, cwd=ROOT)
@@ -324,7 +324,7 @@ def test_provider_hbm_store_declines_over_tcp(require_gpu, tmp_path, streams, lo
 
 def test_bench_api_mof_files(require_gpu, tmp_path):
     """bench.py --api --mof-dir: TeraSort with Hadoop-written MOF files through the C ABI."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--api", "--mof-dir", str(tmp_path), "--rows-per-gpu",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--api", "--mof-dir", str(tmp_path), "--rows-per-gpu",
            "2000000", "--maps-per-gpu", "4", "--reducers", "4", "--steps", "2", "--warmup", "1"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -339,7 +339,7 @@ def test_bench_api_mof_files(require_gpu, tmp_path):
 def test_bench_api_secondary_sort_skew(require_gpu):
     """bench.py --api --workload secondary: config #5 through the C ABI (device-generated variable-length
     Text MOFs, 60% of the records in reduce task 0, key-range rounds bounding the merge's HBM)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--api", "--workload", "secondary", "--rows-per-gpu",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--api", "--workload", "secondary", "--rows-per-gpu",
            "6000000", "--maps-per-gpu", "8", "--reducers", "4", "--round-mb", "64", "--steps", "2", "--warmup", "1"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -434,7 +434,7 @@ def test_hybrid_task_over_device_mofs_takes_device_path(require_gpu, provider, t
 def test_bench_api_compressed_mofs(require_gpu, codec):
     """bench.py --api --api-codec: compressed TeraSort MOFs in HBM, decoded on the device from the
     descriptors by every reduce task, validated."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--api", "--api-codec", codec, "--rows-per-gpu", "2000000",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--api", "--api-codec", codec, "--rows-per-gpu", "2000000",
            "--maps-per-gpu", "4", "--reducers", "4", "--steps", "2", "--warmup", "1"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -110,7 +110,7 @@ def test_ipc_exchange_refuses_mismatch_and_host_source(require_gpu):
 
 
 def _bench(*extra, timeout=600):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
            "--d2h-piece-mb", "8", "--pinned-slots", "4", *extra]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-4000:]

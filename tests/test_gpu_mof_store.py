@@ -181,7 +181,7 @@ def test_bench_node_shape_small(require_gpu, service):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--api", "--node", "--reducers", "3", "--rows-per-gpu",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--api", "--node", "--reducers", "3", "--rows-per-gpu",
            "3000000", "--maps-per-gpu", "6", "--steps", "1", "--warmup", "1", "--node-service" if service else "--no-node-service"]
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -247,7 +247,7 @@ def test_bench_node_files_default_configuration(require_gpu, tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k != "UDA_API_CONF"}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--api", "--node", "--mof-dir", str(tmp_path), "--reducers",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--api", "--node", "--mof-dir", str(tmp_path), "--reducers",
            "3", "--rows-per-gpu", "3000000", "--maps-per-gpu", "6", "--steps", "1", "--warmup", "1"]
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -67,7 +67,7 @@ def _run(fake_jvm, manifest):
 
 
 @pytest.mark.parametrize("codec,service", [(None, False), ("snappy", False), (None, True)])
-def test_jni_reduce_through_fake_jvm(native, fake_jvm, tmp_path, codec, service):
+def test_jni_reduce_through_fake_jvm(native, fake_jvm, tmp_path, sock_dir, codec, service):
     """With the merge service, dataFromUda / fetchOverMessage come from the client's socket threads:
     the shim must attach them like any other native thread."""
     maps = datagen.secondary_sort(num_maps=9, reducers=2, rows_per_map=400, seed=31)
@@ -77,7 +77,7 @@ def test_jni_reduce_through_fake_jvm(native, fake_jvm, tmp_path, codec, service)
         mid = f"attempt_{job}_m_{i:06d}_0"
         mofs[mid] = write_mof(str(tmp_path), mid, parts, codec=codec)
     m = str(tmp_path / "manifest.txt")
-    _manifest(native, m, mofs, maps, job, 1, codec=codec, service=str(tmp_path / "svc.sock") if service else None)
+    _manifest(native, m, mofs, maps, job, 1, codec=codec, service=os.path.join(sock_dir, "svc.sock") if service else None)
     st = _run(fake_jvm, m)
     assert st["onload_version"] == 0x00010004
     assert st["start_rc"] == 0 and st["finished"] and st["failures"] == 0

@@ -5,6 +5,7 @@ multi-process shape (fresh task processes) is covered by tests/test_reduce_task_
 
 Reference: the NetMerger runs inside each reduce task's JVM (src/UdaBridge.cc:187-263); here it can run
 in the provider process (csrc/service/merge_service.h) with the same host contract."""
+import os
 import socket
 import threading
 
@@ -19,11 +20,11 @@ def _port():
         return s.getsockname()[1]
 
 
-def test_service_hosted_tasks_in_one_process(native, tmp_path):
+def test_service_hosted_tasks_in_one_process(native, sock_dir):
     """Four reduce tasks at once, each a client of the service in the same process; records, order and
     the fetch-over / stats callbacks as with in-process tasks."""
     port = _port()
-    path = str(tmp_path / "svc.sock")
+    path = os.path.join(sock_dir, "svc.sock")
     prov = UdaProvider(transport="tcp", data_port=port,
                        conf={"mapred.uda.provider.bind.address": "127.0.0.1", "mapred.uda.gpu.merge.service": path})
     try:
@@ -60,7 +61,7 @@ def test_service_hosted_tasks_in_one_process(native, tmp_path):
         prov.close()
 
 
-def test_unreachable_service_merges_in_process(native, tmp_path):
+def test_unreachable_service_merges_in_process(native, sock_dir):
     port = _port()
     prov = UdaProvider(transport="tcp", data_port=port, conf={"mapred.uda.provider.bind.address": "127.0.0.1"})
     try:
@@ -74,7 +75,7 @@ def test_unreachable_service_merges_in_process(native, tmp_path):
             ids.append(mid)
         c = UdaConsumer(3, job, f"attempt_{job}_r_000000_0", datagen.TEXT, transport="tcp", data_port=port,
                         conf={"mapred.uda.merge.backend": "cpu",
-                              "mapred.uda.gpu.merge.service": str(tmp_path / "nobody.sock")})
+                              "mapred.uda.gpu.merge.service": os.path.join(sock_dir, "nobody.sock")})
         for m in ids:
             c.fetch("127.0.0.1", job, m, 0)
         assert c.wait(60) == sorted(kv for m in maps for kv in m[0])

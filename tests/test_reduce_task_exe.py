@@ -91,8 +91,8 @@ def test_provider_releases_the_connections_of_finished_tasks(native):
         prov.close()
 
 
-def _service_provider(tmp_path, port):
-    path = str(tmp_path / "merge.sock")
+def _service_provider(sock_dir, port):
+    path = os.path.join(sock_dir, "merge.sock")
     prov = UdaProvider(transport="tcp", data_port=port, conf={"mapred.uda.provider.bind.address": "127.0.0.1",
                                                               "mapred.uda.gpu.merge.service": path})
     job = "job_8_0001"
@@ -107,13 +107,13 @@ def _service_provider(tmp_path, port):
 
 
 @pytest.mark.skipif(not os.access(EXE, os.X_OK), reason="uda_reduce_task not built")
-def test_reduce_tasks_hosted_by_the_merge_service(native, tmp_path):
+def test_reduce_tasks_hosted_by_the_merge_service(native, sock_dir):
     """mapred.uda.gpu.merge.service: the reduce task processes are thin clients; their NetMergers run in
     the provider's process (commands, configuration pulls, dataFromUda and the stats cross a Unix
     socket). Three tasks at once, each must deliver its partition in order."""
     import concurrent.futures as cf
     port = _port()
-    prov, path, job, maps, ids = _service_provider(tmp_path, port)
+    prov, path, job, maps, ids = _service_provider(sock_dir, port)
     try:
         def run(r):
             want = sum(len(m[r]) for m in maps)
@@ -129,12 +129,12 @@ def test_reduce_tasks_hosted_by_the_merge_service(native, tmp_path):
 
 
 @pytest.mark.skipif(not os.access(EXE, os.X_OK), reason="uda_reduce_task not built")
-def test_merge_service_survives_a_dead_client_and_reports_failures(native, tmp_path):
+def test_merge_service_survives_a_dead_client_and_reports_failures(native, sock_dir):
     """A client killed mid-task leaves the service serving the next task; a task whose FETCH names a map
     the provider does not have fails in its own process (failureInUda), as an in-process task would;
     an unreachable service means the task merges in its own process."""
     port = _port()
-    prov, path, job, maps, ids = _service_provider(tmp_path, port)
+    prov, path, job, maps, ids = _service_provider(sock_dir, port)
     try:
         argv = [EXE, "-D", "mapred.uda.transport=tcp", "-D", "mapred.uda.merge.backend=cpu",
                 "-D", f"mapred.uda.gpu.merge.service={path}", "--", "-w", "256", "-r", str(port), "-a", "1", "-m",
@@ -155,19 +155,19 @@ def test_merge_service_survives_a_dead_client_and_reports_failures(native, tmp_p
                         extra=["-D", f"mapred.uda.gpu.merge.service={path}"])
         assert rc == 1 and out["error"], out
         rc, out = _task(native, port, job, ids, 0, sum(len(m[0]) for m in maps),
-                        extra=["-D", f"mapred.uda.gpu.merge.service={tmp_path}/none.sock"])
+                        extra=["-D", f"mapred.uda.gpu.merge.service={sock_dir}/none.sock"])
         assert rc == 0 and "merge_service" not in out["task"], out
     finally:
         prov.close()
 
 
 @pytest.mark.skipif(not os.access(EXE, os.X_OK), reason="uda_reduce_task not built")
-def test_task_fails_cleanly_when_the_merge_service_goes_away(native, tmp_path):
+def test_task_fails_cleanly_when_the_merge_service_goes_away(native, sock_dir):
     """The service's process ends while a hosted task waits for its remaining FETCHes: the task
     process reports the failure (failureInUda -> Hadoop's vanilla shuffle) and exits instead of hanging."""
     import time
     port = _port()
-    prov, path, job, maps, ids = _service_provider(tmp_path, port)
+    prov, path, job, maps, ids = _service_provider(sock_dir, port)
     try:
         argv = [EXE, "-D", "mapred.uda.transport=tcp", "-D", "mapred.uda.merge.backend=cpu",
                 "-D", f"mapred.uda.gpu.merge.service={path}", "--", "-w", "256", "-r", str(port), "-a", "1", "-m",

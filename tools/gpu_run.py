@@ -191,6 +191,12 @@ for k, counters in ROOF_PASSES.items():
                                      f"python3 tools/hbm_copy_roof.py")
 
 
+# every bench recipe reports "validated": the validated step of bench.py is behind --full
+for name, (seconds, cmd) in list(RECIPES.items()):
+    if "bench.py" in cmd and "--no-validate" not in cmd:
+        RECIPES[name] = (seconds, cmd.replace("bench.py", "bench.py --full"))
+
+
 def summarize(path: str, keys: list[str]) -> str:
     line = None
     try:

@@ -75,6 +75,8 @@ class TeraSortShuffle:
             validate=cfg.validate, store=cfg.store, local_dirs=cfg.local_dirs, replan=cfg.replan,
             map_sort=cfg.map_sort, check_delivery=cfg.check_delivery))
         self.sink = n.J2CSink(cfg.reducers, cfg.kv_buf_bytes)
+        self.sampler = None                 # sample_outputs(): a StreamSampler beside the sink
+        self.sample_index = []
         self.expected_checksum = None
         self.expected_records = None
         self.setup_s = {}
@@ -164,6 +166,8 @@ class TeraSortShuffle:
         reducer, framing, EOF); validate=True also runs the device order/checksum/exchange checks."""
         if self.sink is not None and self.cfg.deliver_host:
             self.sink.reset()
+        if self.sampler is not None:
+            self.sampler.reset()
         st = self.job.run_step(self.cfg.validate if validate is None else validate)
         if self.sink is not None and self.cfg.deliver_host:
             self.sink.flush()  # the reduce tasks' threads walked every delivered KVBuf
@@ -172,13 +176,35 @@ class TeraSortShuffle:
             st["consumer_eof"] = [self.sink.eof(i) for i in range(self.cfg.reducers)]
         return st
 
+    def sample_outputs(self, records_per_reducer: int, seed: int = 0) -> None:
+        """From now on every step keeps a fixed sample of what the reducers' consumers receive: about
+        `records_per_reducer` whole records of every reducer's merged stream, the first and the last
+        among them, at record numbers drawn once from `seed` and the planned record counts. The
+        consumers still get every buffer (the J2C sink runs as before). After setup()."""
+        if self.sink is None or not self.cfg.deliver_host:
+            raise RuntimeError("sample_outputs needs the host delivery into the J2C sink")
+        self.sample_index = []
+        for r, n in enumerate(self.job.reducer_records()):
+            rng = np.random.RandomState((seed + r) % (1 << 32))
+            idx = rng.randint(0, max(1, n), size=max(0, records_per_reducer - 2)) if n > 0 else np.zeros(0, np.int64)
+            edge = np.asarray([0, n - 1] if n > 0 else [], np.int64)
+            self.sample_index.append(np.unique(np.concatenate([idx.astype(np.int64), edge])))
+        self.sampler = native().StreamSampler([(i * RECORD_BYTES).tolist() for i in self.sample_index], RECORD_BYTES)
+        self.job.set_j2c_sink(self.sink, self.sampler)
+
+    def sampled_outputs(self) -> list[np.ndarray]:
+        """Per reducer, the sampled records of the last step: (len(sample_index[r]), RECORD_BYTES) uint8."""
+        return [np.asarray(self.sampler.data(r)) for r in range(self.cfg.reducers)]
+
     def drop_sink(self) -> None:
         """Ablation: delivered buffers are released unread (no consumer work)."""
+        self.sampler = None
         self.sink = None
         self.job.clear_sink()
 
     def use_python_sink(self, fn, with_reducer: bool = False) -> None:
         """Deliver to a Python callable instead of the native J2C sink (tests)."""
+        self.sampler = None
         self.sink = None
         self.job.set_python_sink(fn, with_reducer)
 
