@@ -179,7 +179,7 @@ def decode(args) -> dict:
     """F6: device block decode of block-compressed IFile runs (secondary-sort data) vs host decode."""
     from uda_amd import native
     n = native()
-    codec = {"snappy": 1, "lzo": 2}[args.codec]
+    codec = {"snappy": 1, "lzo": 2, "lz4": 3}[args.codec]
     rows = int(args.gb * 1e9 / 100 / args.maps)
     runs = [m[0] for m in n.generate_runs("secondary", args.maps, 1, rows, 5)]
     t0 = time.perf_counter()
@@ -460,7 +460,7 @@ def main() -> int:
     ap.add_argument("config", choices=["wordcount_loopback", "wordcount_tcp", "cpu_reference", "secondary_sort", "spill", "decode", "aio",
                                        "netmerger", "radix", "hybrid_budget"])
     ap.add_argument("--dir", default="/tmp")
-    ap.add_argument("--codec", default="snappy", choices=["snappy", "lzo"])
+    ap.add_argument("--codec", default="snappy", choices=["snappy", "lzo", "lz4"])
     ap.add_argument("--gb", type=float, default=1.0)
     ap.add_argument("--maps", type=int, default=16)
     ap.add_argument("--reducers", type=int, default=4)

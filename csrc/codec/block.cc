@@ -12,6 +12,7 @@ Codec codec_from_class(const std::string& cls, bool* unsupported) {
   if (cls.empty() || cls == "null") return Codec::kNone;
   if (cls.find("SnappyCodec") != std::string::npos) return Codec::kSnappy;
   if (cls.find("LzoCodec") != std::string::npos || cls.find("LzopCodec") != std::string::npos) return Codec::kLzo;
+  if (cls.find("Lz4Codec") != std::string::npos) return Codec::kLz4;  // beyond the reference
   *unsupported = true;  // getCompAlg (reducer.cc:439-450) throws on anything else
   return Codec::kNone;
 }
@@ -20,6 +21,7 @@ const char* codec_name(Codec c) {
   switch (c) {
     case Codec::kSnappy: return "snappy";
     case Codec::kLzo: return "lzo1x";
+    case Codec::kLz4: return "lz4";
     default: return "none";
   }
 }
@@ -50,6 +52,9 @@ std::vector<uint8_t> block_compress(Codec c, const uint8_t* src, size_t n, size_
     } else if (c == Codec::kLzo) {
       tmp.resize(lzo1x_max_compressed_length(len));
       clen = lzo1x_compress(src + off, len, tmp.data());
+    } else if (c == Codec::kLz4) {
+      tmp.resize(lz4_max_compressed_length(len));
+      clen = lz4_compress(src + off, len, tmp.data());
     } else {
       throw UdaError("block_compress: no codec");
     }
@@ -90,9 +95,15 @@ bool BlockDecoder::decode_some() {
   const size_t base = out_.size();
   out_.resize(base + (size_t)block_remaining_);
   size_t got = 0;
-  bool ok = (codec_ == Codec::kSnappy)
-                ? snappy_decompress(src, clen, out_.data() + base, (size_t)block_remaining_, &got)
-                : lzo1x_decompress(src, clen, out_.data() + base, (size_t)block_remaining_, &got);
+  bool ok = false;
+  uint8_t* const dst = out_.data() + base;
+  const size_t cap = (size_t)block_remaining_;  // LZO / LZ4 chunks carry no length: `got` says what came out
+  switch (codec_) {
+    case Codec::kSnappy: ok = snappy_decompress(src, clen, dst, cap, &got); break;
+    case Codec::kLzo: ok = lzo1x_decompress(src, clen, dst, cap, &got); break;
+    case Codec::kLz4: ok = lz4_decompress(src, clen, dst, cap, &got); break;
+    default: throw UdaError("BlockDecoder: no decoder for codec " + std::to_string((int)codec_));
+  }
   if (!ok) throw UdaError(std::string("corrupt ") + codec_name(codec_) + " block");
   out_.resize(base + got);
   block_remaining_ -= (int64_t)got;

@@ -2869,7 +2869,7 @@ bool ReduceTask::merge_gpu_device(bool probe) {
       ws.decoder.decode(codec_, bp, nullptr, ws.in.as<uint8_t>(), s);
       roff = bp.raw_offset;
       blocks = (int64_t)bp.descs.size();
-    } else {  // framing that needs a decode (multi-chunk LZO blocks): decode on the host
+    } else {  // framing that needs a decode (multi-chunk LZO or LZ4 blocks): decode on the host
       UDA_LOG(kInfo, "device decode: framing needs a host decode (%s)", codec_name(codec_));
       std::vector<std::vector<uint8_t>> raws;
       roff.assign(1, 0);

@@ -297,7 +297,10 @@ void ApiTeraSortBench::setup() {
 // raw bytes it replaces; checked), and only then is the compressed store allocated -- raw and
 // compressed copies never share HBM, and the host holds one copy plus a partition per thread.
 void ApiTeraSortBench::compress_store() {
-  const Codec c = cfg_.codec == "snappy" ? Codec::kSnappy : cfg_.codec == "lzo" ? Codec::kLzo : Codec::kNone;
+  const Codec c = cfg_.codec == "snappy" ? Codec::kSnappy
+                  : cfg_.codec == "lzo"  ? Codec::kLzo
+                  : cfg_.codec == "lz4"  ? Codec::kLz4
+                                         : Codec::kNone;
   if (c == Codec::kNone) throw std::runtime_error("api bench: unknown codec " + cfg_.codec);
   const int P = cfg_.world * cfg_.reducers, M = cfg_.maps;
   std::vector<int64_t> raw_off((size_t)M + 1, 0);
@@ -410,6 +413,7 @@ std::vector<std::string> ApiTeraSortBench::task_commands(int r) const {
   std::snprintf(rt, sizeof(rt), "attempt_%s_r_%06d_0", cfg_.job.c_str() + 4, g);
   const std::string codec_cls = cfg_.codec == "snappy" ? "org.apache.hadoop.io.compress.SnappyCodec"
                                 : cfg_.codec == "lzo"  ? "com.hadoop.compression.lzo.LzoCodec"
+                                : cfg_.codec == "lz4"  ? "org.apache.hadoop.io.compress.Lz4Codec"
                                                        : "null";
   std::vector<std::string> out;
   const std::vector<std::string> init = {std::to_string(W * cfg_.maps), cfg_.job, rt, "0", std::to_string(1 << 20),

@@ -57,7 +57,7 @@ struct ApiBenchConfig {
   // map's records in reduce task 0 of every rank (BASELINE config #5; device generator secgen.h)
   std::string workload = "terasort";
   double skew = 0.6;
-  // "snappy" / "lzo": every partition is block-compressed (256 KiB blocks) at setup and the compressed
+  // "snappy" / "lzo" / "lz4": every partition is block-compressed (256 KiB blocks) at setup and the compressed
   // MOFs are registered in HBM; INIT announces the codec, so reduce tasks decode on the device (F6)
   std::string codec;
 };

@@ -37,7 +37,7 @@ bool plan_block_streams(Codec codec, const std::vector<const uint8_t*>& ptrs, co
         if (i + 4 > n) return false;
         const int64_t clen = be32(p + i);
         if (i + 4 + clen > n) return false;
-        int64_t produced = left;  // LZO: a single chunk must produce the whole block
+        int64_t produced = left;  // LZO, LZ4: a chunk carries no length, so a single chunk must produce the whole block
         if (codec == Codec::kSnappy) {
           size_t ulen = 0;
           if (!snappy_uncompressed_length(p + i + 4, (size_t)clen, &ulen)) return false;

@@ -21,7 +21,7 @@ struct BlockPlan {
 
 // Walk the framing of each stream (`offs[i]`..`offs[i]+lens[i]` of one host buffer, or of separate
 // buffers when ptrs is given). Returns false when the framing cannot be resolved without decoding
-// (an LZO block split into several chunks) or is malformed; the caller then decodes on the host.
+// (an LZO or LZ4 block split into several chunks) or is malformed; the caller then decodes on the host.
 bool plan_block_streams(Codec codec, const std::vector<const uint8_t*>& ptrs, const std::vector<int64_t>& lens,
                         BlockPlan* plan);
 

@@ -1,4 +1,4 @@
-// F6 — block-decompress kernels (Snappy raw format, LZO1X) for Hadoop block-compressed map
+// F6 — block-decompress kernels (Snappy raw format, LZO1X, LZ4 block format) for Hadoop block-compressed map
 // outputs, decoded in HBM so the compressed bytes are what crosses PCIe / the network.
 //
 // Reference: DecompressorWrapper::doDecompress (src/Merger/DecompressorWrapper.cc:168-197) feeding
@@ -11,11 +11,13 @@
 //   * a back-reference that reads bytes this wave stored since the last store fence first waits
 //     for its stores (workgroup-scope fence: the wave's own stores are visible through the CU's
 //     write-through L1 once they completed).
-// Format parity with the host decoders in csrc/codec/{snappy,lzo}.cc (same bounds checks); a
-// corrupt block sets its status word and the caller raises.
+// Format parity with the host decoders in csrc/codec/{snappy,lzo,lz4}.cc (same bounds checks); a
+// corrupt block sets its status word and the caller raises. LZ4 (Hadoop's Lz4Codec) has no counterpart
+// in the reference; it decodes with the lean wave parse only (lz4_lean_kernel).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <stdexcept>
 #include <string>
 
 #include "kernels.h"
@@ -583,6 +585,113 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock)
   if (!ok && lane == 0) atomicOr(status, 1);
 }
 
+// ---- LZ4 block format (csrc/codec/lz4.cc), the lean wave parse with one token layout:
+//   token (literal length << 4 | match length - 4), literal-length extension, literals, 2-byte LE offset,
+//   match-length extension; the chunk ends right after a literal run.
+// Same window, literal and match helpers as the LZO lean kernel. Unlike LZO1X the stream has no end
+// marker, so nothing about a token's bytes is implied by the previous check: the token needs ip < ip_end,
+// the offset ip + 2 <= ip_end, every extension byte its own test. lean_peek4 reads zeros past the chunk
+// end, so a peek is always safe to take; its bytes are only used after the test that says they exist.
+// Lengths are compared against what is left (len > oend - op), and inside the extension runs, so a long
+// run of 0xFF neither wraps a 32-bit length nor parses further than the chunk could use.
+template <bool P>
+__device__ bool lz4_lean_chunk(const uint8_t* ib, uint8_t* ob, uint32_t ip, const uint32_t ip_end, uint32_t op,
+                               const uint32_t oend, const uint32_t clip, uint32_t& flushed, const int lane,
+                               uint32_t* produced) {
+  LeanWin w;
+  const uint32_t out0 = op;
+  for (;;) {
+    if (P && op >= clip) {  // prefix decode: everything wanted is out
+      *produced = oend - out0;
+      return true;
+    }
+    if (ip >= ip_end) return false;  // a token is due
+    const uint32_t v = lean_peek4(w, ib, ip, ip_end, lane);
+    const uint32_t token = v & 0xFF;
+    ++ip;
+    uint32_t len = token >> 4;
+    uint32_t off = 0;
+    if (len < 2) {
+      // 0 or 1 literals: the offset is in the token's peek (believed only after the bounds test below)
+      off = (v >> (8 + 8 * len)) & 0xFFFF;
+    } else if (len == 15) {
+      uint32_t b;
+      do {
+        if (ip >= ip_end) return false;
+        b = lean_peek4(w, ib, ip, ip_end, lane) & 0xFF;
+        ++ip;
+        len += b;
+        if (len > ip_end - ip) return false;
+      } while (b == 255);
+    }
+    if (len > ip_end - ip || len > oend - op) return false;
+    lean_literal<P>(w, ib, ob, op, ip, ip_end, len, clip, lane);
+    ip += len;
+    op += len;
+    if (ip == ip_end) {  // the one valid ending: right after a literal run
+      *produced = op - out0;
+      return true;
+    }
+    if (ip_end - ip < 2) return false;
+    if (len >= 2) off = lean_peek4(w, ib, ip, ip_end, lane) & 0xFFFF;
+    ip += 2;
+    if (off == 0 || off > op - out0) return false;  // offsets reach back to this chunk's start at most
+    len = token & 15;
+    if (len == 15) {
+      uint32_t b;
+      do {
+        if (ip >= ip_end) return false;
+        b = lean_peek4(w, ib, ip, ip_end, lane) & 0xFF;
+        ++ip;
+        len += b;
+        if (len > oend - op) return false;
+      } while (b == 255);
+    }
+    len += 4;
+    if (len > oend - op) return false;
+    lean_match<P>(ob, op, off, len, clip, flushed, lane);
+    op += len;
+  }
+}
+
+template <bool P>
+__global__ void __launch_bounds__(64 * kWavesPerBlock)
+    lz4_lean_kernel(const uint8_t* in, uint8_t* out, const DecodeDesc* descs, int n, int* status, int64_t clip_in) {
+  // wave-uniform block index (see lzo_lean_kernel): the parse lives in SGPRs
+  const int b = blockIdx.x * kWavesPerBlock + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (b >= n) return;
+  const DecodeDesc d = descs[b];
+  const int lane = threadIdx.x & 63;
+  const uint8_t* ib = in + d.src;
+  uint8_t* ob = out + d.dst;
+  const int64_t ilen = d.src_end - d.src;
+  bool ok = ilen >= 0 && ilen < (1ll << 31) && d.raw >= 0 && d.raw < (1ll << 31);
+  const uint32_t ie = ok ? (uint32_t)ilen : 0, oend = ok ? (uint32_t)d.raw : 0;
+  const uint32_t clip = P ? (uint32_t)min(clip_in, (int64_t)oend) : oend;
+  uint32_t ip = 0, op = 0, flushed = 0;
+  // one block = one or more [u32 BE compressed_len][chunk] records until its raw bytes are produced; a
+  // chunk that produces nothing still consumes its header, so bad input cannot keep the wave here
+  while (ok && op < oend) {
+    if (P && op >= clip) return;  // prefix decode done
+    if (ie - ip < 4) {
+      ok = false;
+      break;
+    }
+    const uint32_t clen = be32(ib + ip);
+    ip += 4;
+    if (clen > ie - ip) {
+      ok = false;
+      break;
+    }
+    uint32_t produced = 0;
+    ok = lz4_lean_chunk<P>(ib, ob, ip, ip + clen, op, oend, clip, flushed, lane, &produced);
+    ip += clen;
+    op += produced;
+  }
+  if (ok && (op != oend || ip != ie)) ok = false;
+  if (!ok && lane == 0) atomicOr(status, 1);
+}
+
 // clip > 0: prefix decode. Only the first `clip` bytes of each block's output (at d.dst) are written and
 // the decode stops once they are out; d.raw stays the block's full raw size for the format checks.
 template <int kCodec, bool R>
@@ -899,7 +1008,7 @@ __global__ void __launch_bounds__(64) frame_streams_kernel(const uint8_t* const*
         bad = 1;
         break;
       }
-      int64_t produced = left;  // LZO: one chunk produces the whole block
+      int64_t produced = left;  // LZO, LZ4: a chunk carries no length, so one chunk produces the whole block
       if (codec == 1) {         // Snappy: the chunk's uncompressed-length varint
         uint64_t u = 0;
         int sh = 0, k = 0;
@@ -952,7 +1061,16 @@ void launch_frame_streams(const uint8_t* const* ptrs, const int64_t* lens, int n
 void launch_block_decode(int codec, const uint8_t* in, uint8_t* out, const DecodeDesc* descs, int n, int* status,
                          hipStream_t s, int64_t clip) {
   if (n <= 0) return;
+  // an unknown codec value launches nothing: no kernel may read a stream as a format it is not
+  if (codec < 1 || codec > 3) throw std::invalid_argument("launch_block_decode: unknown codec " + std::to_string(codec));
   const int grid = (n + kWavesPerBlock - 1) / kWavesPerBlock;
+  if (codec == 3) {  // LZ4: one kernel, no knobs (UDA_DECODE_WINDOW / UDA_LZO_LANE do not apply)
+    if (clip > 0)
+      lz4_lean_kernel<true><<<grid, 64 * kWavesPerBlock, 0, s>>>(in, out, descs, n, status, clip);
+    else
+      lz4_lean_kernel<false><<<grid, 64 * kWavesPerBlock, 0, s>>>(in, out, descs, n, status, clip);
+    return;
+  }
   // read per launch: tests compare the kernels in one process
   const char* le = std::getenv("UDA_LZO_LANE");  // 1: one lane per LZO block (too few blocks per round to hide latency)
   const bool lzo_lane = le && std::atoi(le) != 0;

@@ -8,7 +8,7 @@
 //   F2 key normalization   -> extract_keys_fixed / extract_keys_generic (+ __device__ compare)
 //   F3 k-way merge         -> merge_partition + merge_pass (pairwise merge-path tree on keys)
 //   F4 serialize / gather  -> gather_fixed / gather_var + buffer cut points
-//   F6 block decompress    -> snappy_decompress_blocks / lzo1x_decompress_blocks
+//   F6 block decompress    -> launch_block_decode (Snappy, LZO1X, LZ4 block format) + launch_frame_streams
 // plus TeraGen-shaped synthetic map-output generation and device-side validation.
 #pragma once
 #include "uda/hash.h"
@@ -242,7 +242,8 @@ struct DecodeDesc {
   int64_t dst;
   int64_t raw;
 };
-// codec: 1 = Snappy, 2 = LZO1X (uda::Codec values). *status |= 1 if any block is corrupt.
+// codec: 1 = Snappy, 2 = LZO1X, 3 = LZ4 (uda::Codec values); any other value throws and launches nothing.
+// *status |= 1 if any block is corrupt.
 // clip > 0: prefix decode, only the first `clip` raw bytes of every block are produced (at its dst).
 void launch_block_decode(int codec, const uint8_t* in, uint8_t* out, const DecodeDesc* descs, int n, int* status,
                          hipStream_t s, int64_t clip = 0);

@@ -3,7 +3,8 @@
 // Parity: DecompressorWrapper + LzoDecompressor + SnappyDecompressor (src/Merger/
 // DecompressorWrapper.cc, LzoDecompressor.cc, SnappyDecompressor.cc). The reference dlopens
 // liblzo2 / libsnappy; neither exists here, so both decoders are implemented in-tree (host C++;
-// the GPU engine has its own per-block device decoders). Framing (Hadoop BlockCompressorStream):
+// the GPU engine has its own per-block device decoders). LZ4 (Hadoop's Lz4Codec, same framing) goes
+// beyond the reference, whose getCompAlg throws on it. Framing (Hadoop BlockCompressorStream):
 //   block := [u32 BE uncompressed_len] { [u32 BE compressed_len][compressed bytes] }+
 // The reference assumes one compressed chunk per block (LzoDecompressor.cc:151-167); we accept
 // several chunks per block, which Hadoop emits when a block's compressed output is split.
@@ -15,9 +16,9 @@
 
 namespace uda {
 
-enum class Codec { kNone = 0, kSnappy = 1, kLzo = 2 };
+enum class Codec { kNone = 0, kSnappy = 1, kLzo = 2, kLz4 = 3 };
 
-// Map a Hadoop codec class name ("...SnappyCodec", "...LzoCodec") to a codec; kNone for ""/null.
+// Map a Hadoop codec class name ("...SnappyCodec", "...LzoCodec", "...Lz4Codec") to a codec; kNone for ""/null.
 // Unsupported names return kNone and set *unsupported.
 Codec codec_from_class(const std::string& cls, bool* unsupported);
 const char* codec_name(Codec c);
@@ -32,6 +33,12 @@ bool snappy_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, s
 size_t lzo1x_max_compressed_length(size_t n);
 size_t lzo1x_compress(const uint8_t* src, size_t n, uint8_t* dst);
 bool lzo1x_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len);
+
+// ---- LZ4 (raw block format, what Hadoop's Lz4Compressor / Lz4Decompressor put in a chunk: no frame
+// header, no stored length). The decoder is the safe variant; the encoder keeps the end-of-block rules.
+size_t lz4_max_compressed_length(size_t n);
+size_t lz4_compress(const uint8_t* src, size_t n, uint8_t* dst);
+bool lz4_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len);
 
 // Compress `n` bytes into Hadoop block framing with blocks of at most `block_size` raw bytes.
 std::vector<uint8_t> block_compress(Codec c, const uint8_t* src, size_t n, size_t block_size);

@@ -316,6 +316,22 @@ PYBIND11_MODULE(_uda_native, m) {
     out.resize(n);
     return py::bytes(out);
   });
+  m.def("lz4_compress", [](py::bytes b) {
+    std::string s = b;
+    std::string out(lz4_max_compressed_length(s.size()), '\0');
+    size_t n = lz4_compress((const uint8_t*)s.data(), s.size(), (uint8_t*)&out[0]);
+    out.resize(n);
+    return py::bytes(out);
+  });
+  m.def("lz4_decompress", [](py::bytes b, size_t cap) {
+    std::string s = b;
+    std::string out(cap, '\0');
+    size_t n = 0;
+    if (!lz4_decompress((const uint8_t*)s.data(), s.size(), (uint8_t*)&out[0], cap, &n))
+      throw py::value_error("corrupt lz4 data");
+    out.resize(n);
+    return py::bytes(out);
+  });
   m.def("codec_from_class", [](const std::string& c) {
     bool unsup = false;
     int v = (int)codec_from_class(c, &unsup);
@@ -1264,7 +1280,11 @@ PYBIND11_MODULE(_uda_native, m) {
   m.def("gpu_block_decode", [](const std::string& codec_cls, const std::vector<std::string>& streams, int device) {
     bool unsup = false;
     Codec c = codec_from_class(codec_cls, &unsup);
-    if (c == Codec::kNone) c = codec_cls == "snappy" ? Codec::kSnappy : codec_cls == "lzo" ? Codec::kLzo : Codec::kNone;
+    if (c == Codec::kNone)
+      c = codec_cls == "snappy" ? Codec::kSnappy
+          : codec_cls == "lzo"  ? Codec::kLzo
+          : codec_cls == "lz4"  ? Codec::kLz4
+                                : Codec::kNone;
     if (c == Codec::kNone) throw py::value_error("unknown codec " + codec_cls);
     std::vector<std::string> outs;
     int64_t blocks = 0;

@@ -106,6 +106,7 @@ class UdaPluginRT extends UdaPlugin implements UdaCallable {
     if (codec == null) return dflt;
     if (codec.contains("Lzo")) return conf.getInt("io.compression.codec.lzo.buffersize", dflt);
     if (codec.contains("Snappy")) return conf.getInt("io.compression.codec.snappy.buffersize", dflt);
+    if (codec.contains("Lz4")) return conf.getInt("io.compression.codec.lz4.buffersize", dflt);
     return dflt;
   }
 

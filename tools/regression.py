@@ -12,7 +12,7 @@ test (utils/master/*.sh). This tool does the same on one node through uda_amd.mo
     python tools/regression.py --matrix m.csv --only wordcount_cpu --samples 1 --scale 0.1
 
 Matrix columns: name, program (terasort|wordcount|secondary), maps, reducers, gb, codec
-(none|snappy|lzo), backend (cpu|gpu), approach (1 online | 2 hybrid), transport (loopback|tcp),
+(none|snappy|lzo|lz4), backend (cpu|gpu), approach (1 online | 2 hybrid), transport (loopback|tcp),
 samples, plus any other ShuffleJobSpec field (e.g. gpu_merge_bytes). GPU rows are skipped when no
 HIP device is visible (reported as SKIP, never as PASS).
 

@@ -44,7 +44,7 @@ class ShuffleJobSpec:
     maps: int = 16
     reducers: int = 4
     gb: float = 0.1                 # total map-output bytes (uncompressed)
-    codec: str | None = None        # None | snappy | lzo
+    codec: str | None = None        # None | snappy | lzo | lz4
     backend: str = "cpu"            # cpu (heap merge, the reference algorithm) | gpu (HIP merge)
     approach: int = 1               # 1 online | 2 hybrid (LPQ spill + RPQ)
     transport: str = "loopback"     # loopback | tcp (provider in another process)

@@ -13,11 +13,12 @@ import zlib
 
 from .._native import native
 
-CODECS = {None: 0, "snappy": 1, "lzo": 2}
+CODECS = {None: 0, "snappy": 1, "lzo": 2, "lz4": 3}
 CODEC_CLASSES = {
     None: None,
     "snappy": "org.apache.hadoop.io.compress.SnappyCodec",
     "lzo": "com.hadoop.compression.lzo.LzoCodec",
+    "lz4": "org.apache.hadoop.io.compress.Lz4Codec",
 }
 
 
