@@ -1,5 +1,6 @@
 // Device shuffle/merge engine implementation. See device_engine.h for the design.
 #include "device_engine.h"
+#include "codec/colpack.h"
 #include "device_ptr.h"
 #include "hbm_ledger.h"
 #include "merge_plan.h"
@@ -767,6 +768,11 @@ ShuffleJob::ShuffleJob(const ShuffleConfig& cfg) : cfg_(cfg) {
   if (cfg_.d2h != "sdma" && cfg_.d2h != "hip") throw std::runtime_error("ShuffleJob: d2h must be sdma or hip");
   if (cfg_.store != "hbm" && cfg_.store != "host" && cfg_.store != "disk")
     throw std::runtime_error("unknown store tier " + cfg_.store);
+  if (cfg_.delivery_pack != "auto" && cfg_.delivery_pack != "off")
+    throw std::runtime_error("ShuffleJob: delivery_pack must be auto or off");
+  pack_ = cfg_.deliver_host && cfg_.delivery_pack == "auto";
+  if (const char* e = std::getenv("UDA_DELIVERY_PACK"))
+    if (std::atoi(e) == 0) pack_ = false;
   R_ = cfg_.reducers;
   Q_ = cfg_.rounds;
   C_ = R_ * Q_;
@@ -786,6 +792,9 @@ ShuffleJob::ShuffleJob(const ShuffleConfig& cfg) : cfg_(cfg) {
   buf_records_ = std::max<int64_t>(1, cfg_.kv_buf_bytes / kTeraRecordBytes);
   const int64_t buf_bytes = buf_records_ * kTeraRecordBytes;
   piece_bytes_ = std::max<int64_t>(1, cfg_.d2h_piece_bytes / buf_bytes) * buf_bytes;
+  // a packed piece of few records is longer than the records themselves (header, padding)
+  ring_stride_ = pack_ ? std::max(piece_bytes_, colpack_bound(kTeraRecordBytes, piece_bytes_ / kTeraRecordBytes))
+                       : piece_bytes_;
   merged_ev_.resize(kSlots);
   comm_ev_.resize(kSlots);
   sent_ev_.resize(2);
@@ -844,8 +853,33 @@ void ShuffleJob::init_ipc(const std::string& name) {
 
 std::string ShuffleJob::delivery_name() const {
   if (!cfg_.deliver_host) return "none";
-  if (sdma_) return sdma_->describe() + " ring=" + ring_numa_;
-  return "hip[numa=" + std::to_string(device_numa_node(cfg_.device)) + "] ring=" + ring_numa_;
+  std::string name = sdma_ ? sdma_->describe() : "hip[numa=" + std::to_string(device_numa_node(cfg_.device)) + "]";
+  name += " ring=" + ring_numa_;
+  if (!pack_) return name + " pack=off";
+  name += " pack=colbits";
+  if (last_d2h_ratio_ >= 0) {  // the last step's d2h_bytes / bytes_in
+    char b[32];
+    std::snprintf(b, sizeof(b), " d2h/in=%.3f", last_d2h_ratio_);
+    name += b;
+  }
+  return name;
+}
+
+std::vector<ShuffleJob::PackPiece> ShuffleJob::round_pieces(const std::vector<int64_t>& group_recs) const {
+  std::vector<PackPiece> v;
+  int64_t goff = 0, doff = 0;
+  for (int i = 0; i < R_; ++i) {
+    const int64_t bytes = group_recs[i] * kTeraRecordBytes;
+    for (int64_t off = 0; off < bytes;) {
+      const int64_t len = std::min(piece_bytes_, bytes - off);
+      const int64_t nrec = len / kTeraRecordBytes;
+      v.push_back(PackPiece{goff + off, doff, nrec});
+      doff += colpack_bound(kTeraRecordBytes, nrec);
+      off += len;
+    }
+    goff += bytes;
+  }
+  return v;
 }
 
 void ShuffleJob::generate() {
@@ -1272,6 +1306,48 @@ void ShuffleJob::compute_plans() {
   out_slots_.clear();
   out_slots_.resize(kSlots);
   for (auto& b : out_slots_) b.alloc(out_bytes);
+  // delivery bit-packing: every D2H piece of a round has a fixed region (its bound, at most 0.9 of the
+  // records plus header and padding) in the packed slot of the round's parity
+  packed_slots_.clear();
+  d_pack_pieces_.clear();
+  d_pack_results_.clear();
+  h_pack_results_.clear();
+  pack_n_.assign(Q_, 0);
+  pack_max_nrec_.assign(Q_, 0);
+  if (pack_) {
+    int64_t packed_bytes = 64;
+    int max_pieces = 1;
+    std::vector<std::vector<PackPiece>> pieces(Q_);
+    for (int q = 0; q < Q_; ++q) {
+      pieces[q] = round_pieces(plans_[q].group_recs);
+      if (pieces[q].size() > 65535) throw std::runtime_error("delivery_pack: more than 65535 D2H pieces in a round");
+      pack_n_[q] = (int)pieces[q].size();
+      max_pieces = std::max(max_pieces, pack_n_[q]);
+      for (const PackPiece& pc : pieces[q]) {
+        pack_max_nrec_[q] = std::max(pack_max_nrec_[q], pc.nrec);
+        packed_bytes = std::max(packed_bytes, pc.dst_off + colpack_bound(kTeraRecordBytes, pc.nrec));
+      }
+    }
+    packed_slots_.resize(kSlots);
+    for (auto& b : packed_slots_) b.alloc((size_t)packed_bytes);
+    d_pack_results_.resize(kSlots);
+    h_pack_results_.resize(kSlots);
+    for (int k = 0; k < kSlots; ++k) {
+      d_pack_results_[k].alloc((size_t)max_pieces * sizeof(ColpackResult));
+      h_pack_results_[k].alloc((size_t)max_pieces * sizeof(ColpackResult));
+    }
+    d_pack_table_.alloc(colpack_table_bytes(max_pieces));
+    d_pack_pieces_.resize(Q_);
+    for (int q = 0; q < Q_; ++q) {
+      if (pieces[q].empty()) continue;
+      std::vector<ColpackPieceDesc> v;
+      for (const PackPiece& pc : pieces[q])
+        v.push_back(ColpackPieceDesc{out_slots_[q % kSlots].as<uint8_t>() + pc.src_off,
+                                     packed_slots_[q % kSlots].as<uint8_t>() + pc.dst_off, pc.nrec});
+      d_pack_pieces_[q].alloc(v.size() * sizeof(ColpackPieceDesc));
+      HIP_CHECK(hipMemcpy(d_pack_pieces_[q].as(), v.data(), v.size() * sizeof(ColpackPieceDesc), hipMemcpyHostToDevice));
+    }
+  }
   recv_slots_.clear();
   if (staged()) {
     recv_slots_.resize(kSlots);
@@ -1415,7 +1491,7 @@ void ShuffleJob::plan() {
   HIP_CHECK(hipSetDevice(cfg_.device));
   compute_plans();
   if (cfg_.deliver_host && !copy_thr_.joinable()) {
-    const size_t ring_bytes = (size_t)piece_bytes_ * cfg_.pinned_slots;
+    const size_t ring_bytes = (size_t)ring_stride_ * cfg_.pinned_slots;
     if (cfg_.d2h == "sdma") {
       sdma_.reset(new SdmaEngine(cfg_.device));
       ring_ = static_cast<uint8_t*>(sdma_->alloc_host(ring_bytes));
@@ -1433,6 +1509,11 @@ void ShuffleJob::plan() {
     items_.assign(R_, {});
     eof_bufs_.clear();
     for (int i = 0; i < R_; ++i) eof_bufs_.emplace_back(new uint8_t[(size_t)cfg_.kv_buf_bytes + 16]);
+    unpack_bufs_.clear();
+    if (pack_) {
+      const size_t one = (size_t)std::max(cfg_.kv_buf_bytes, buf_records_ * kTeraRecordBytes) + 16;
+      for (int i = 0; i < R_; ++i) unpack_bufs_.emplace_back(new uint8_t[2 * one]);
+    }
     copy_thr_ = std::thread([this] { name_thread("uda-copy"); copy_loop(); });
     for (int i = 0; i < R_; ++i) consumers_.emplace_back([this, i] { name_thread("uda-consume"); consume_loop(i); });
   }
@@ -1489,6 +1570,10 @@ void ShuffleJob::copy_loop() {
       }
       std::vector<int> used;
       int64_t goff = 0;
+      // packed rounds: piece p of round_pieces(), its length and flag as the plan kernel wrote them
+      const std::vector<PackPiece> ppieces = pack_ ? round_pieces(r.group_recs) : std::vector<PackPiece>();
+      const ColpackResult* pres = pack_ ? h_pack_results_[r.slot].as<ColpackResult>() : nullptr;
+      size_t pi = 0;
       for (int i = 0; i < R_; ++i) {
         const int64_t bytes = r.group_recs[i] * kTeraRecordBytes;
         if (bytes == 0 && last_round) {
@@ -1517,20 +1602,37 @@ void ShuffleJob::copy_loop() {
               }
             pinned_free_[k] = false;
           }
-          uint8_t* dst = ring_ + (int64_t)k * piece_bytes_;
+          uint8_t* dst = ring_ + (int64_t)k * ring_stride_;
           const uint8_t* from = src + goff + off;
+          int64_t copy_len = len;
+          bool packed = false;
+          if (pack_) {
+            if (pi >= ppieces.size() || ppieces[pi].src_off != goff + off || ppieces[pi].nrec * kTeraRecordBytes != len)
+              throw std::runtime_error("delivery_pack: piece list out of step with the copy loop");
+            const ColpackResult pr = pres[pi];
+            if (pr.packed) {
+              if (pr.bytes < (int64_t)kColpackHeaderBytes || pr.bytes > colpack_bound(kTeraRecordBytes, ppieces[pi].nrec))
+                throw std::runtime_error("delivery_pack: packed length outside the piece's region");
+              packed = true;
+              copy_len = pr.bytes;
+              from = packed_slots_[r.slot].as<uint8_t>() + ppieces[pi].dst_off;
+            }
+            ++pi;
+          }
           if (sdma_) {
-            SdmaEngine::arm(piece_sig_[k], sdma_->parts((size_t)len, cfg_.d2h_engines));
-            sdma_->copy_d2h(dst, from, (size_t)len, piece_sig_[k], cfg_.d2h_engines);
+            SdmaEngine::arm(piece_sig_[k], sdma_->parts((size_t)copy_len, cfg_.d2h_engines));
+            sdma_->copy_d2h(dst, from, (size_t)copy_len, piece_sig_[k], cfg_.d2h_engines);
           } else {
-            HIP_CHECK(hipMemcpyAsync(dst, from, (size_t)len, hipMemcpyDeviceToHost, s_copy_));
+            HIP_CHECK(hipMemcpyAsync(dst, from, (size_t)copy_len, hipMemcpyDeviceToHost, s_copy_));
             HIP_CHECK(hipEventRecord(piece_ev_[k], s_copy_));
           }
           off += len;
           used.push_back(k);
           {
             std::lock_guard<std::mutex> g(mu_);
-            items_[i].push_back(Item{k, len, last_round && off >= bytes, now_ms(), r.q});
+            items_[i].push_back(Item{k, len, last_round && off >= bytes, now_ms(), r.q, packed, copy_len});
+            step_d2h_bytes_ += copy_len;
+            ++(packed ? step_packed_ : step_raw_);
           }
           cv_.notify_all();
         }
@@ -1565,6 +1667,8 @@ void ShuffleJob::consume_loop(int i) {
     HIP_CHECK(hipSetDevice(cfg_.device));
     const int64_t buf_bytes = buf_records_ * kTeraRecordBytes;
     uint8_t* eb = eof_bufs_[i].get();
+    const size_t unpack_one = (size_t)std::max(cfg_.kv_buf_bytes, buf_bytes) + 16;
+    int64_t unpack_turn = 0;  // the two staging buffers alternate
     for (;;) {
       Item it;
       bool check;
@@ -1581,19 +1685,47 @@ void ShuffleJob::consume_loop(int i) {
       int64_t nb = 0;
       double waited = 0;
       bool eof_sent = false;
+      double unpack_ms = 0;
       if (it.pslot >= 0) {
         if (sdma_)
           SdmaEngine::wait(piece_sig_[it.pslot]);
         else
           HIP_CHECK(hipEventSynchronize(piece_ev_[it.pslot]));
         waited = now_ms() - it.issued_ms;
-        const uint8_t* base = ring_ + (int64_t)it.pslot * piece_bytes_;
-        if (check)
+        const uint8_t* base = ring_ + (int64_t)it.pslot * ring_stride_;
+        ColpackPiece pp;
+        if (it.packed) {  // a header that fails its checks fails the step and is never unpacked
+          const char* why = "";
+          if (!colpack_open(base, it.copied, kTeraRecordBytes, it.bytes / kTeraRecordBytes, &pp, &why) || !pp.packed)
+            throw std::runtime_error(std::string("packed piece rejected: ") + (pp.hdr ? "not marked packed" : why));
+        }
+        if (check && !it.packed)
           for (int64_t off = 0; off + kTeraRecordBytes <= it.bytes; off += kTeraRecordBytes)
             got_ck += record_hash(base + off, kTeraRecordBytes);
         for (int64_t off = 0; off < it.bytes; off += buf_bytes) {
           const int64_t len = std::min(buf_bytes, it.bytes - off);
           const bool final_chunk = it.last && off + len >= it.bytes;
+          if (it.packed) {  // unpack this buffer's rows into a staging buffer; the sink gets that
+            uint8_t* stg = unpack_bufs_[i].get() + (size_t)(unpack_turn++ & 1) * unpack_one;
+            if (check || (sink_ && !err)) {  // no sink: nothing is unpacked
+              const double tu = now_ms();
+              colpack_unpack(pp, off / kTeraRecordBytes, len / kTeraRecordBytes, stg);
+              unpack_ms += now_ms() - tu;
+            }
+            if (check)
+              for (int64_t o = 0; o + kTeraRecordBytes <= len; o += kTeraRecordBytes)
+                got_ck += record_hash(stg + o, kTeraRecordBytes);
+            if (final_chunk && len + kEofBytes <= cfg_.kv_buf_bytes) {
+              stg[len] = 0xFF;
+              stg[len + 1] = 0xFF;
+              if (sink_ && !err) err = sink_(i, stg, len + kEofBytes);
+              eof_sent = true;
+            } else if (sink_ && !err) {
+              err = sink_(i, stg, len);
+            }
+            ++nb;
+            continue;
+          }
           if (final_chunk && len + kEofBytes <= cfg_.kv_buf_bytes) {
             std::memcpy(eb, base + off, (size_t)len);
             eb[len] = 0xFF;
@@ -1618,6 +1750,7 @@ void ShuffleJob::consume_loop(int i) {
         if (check && it.q >= 0 && it.q < Q_) delivered_ck_[(size_t)it.q * R_ + i] += got_ck;
         step_buffers_ += nb;
         step_d2h_ms_ += waited;
+        step_unpack_ms_ += unpack_ms;
         if (err && !step_error_) step_error_ = err;
         if (it.last) ++eof_count_;
       }
@@ -1734,6 +1867,8 @@ StepStats ShuffleJob::run_step(bool validate) {
     step_buffers_ = 0;
     step_error_ = 0;
     step_d2h_ms_ = 0;
+    step_d2h_bytes_ = step_packed_ = step_raw_ = 0;
+    step_unpack_ms_ = 0;
     step_check_delivery_ = validate && cfg_.check_delivery && deliver;
     pre_d2h_ck_.assign((size_t)Q_ * R_, 0);
     delivered_ck_.assign((size_t)Q_ * R_, 0);
@@ -2025,6 +2160,13 @@ StepStats ShuffleJob::run_step(bool validate) {
       check_inputs(1);
     }
     HIP_CHECK(hipEventRecord(ev[4 * q + 3], s_compute_));
+    if (pack_ && deliver && pack_n_[q] > 0) {  // bit-pack the round's D2H pieces; lengths and flags to the copy thread
+      launch_colpack(d_pack_pieces_[q].as<ColpackPieceDesc>(), pack_n_[q], pack_max_nrec_[q], kTeraRecordBytes,
+                     buf_records_, d_pack_table_.as<uint32_t>(), d_pack_results_[slot].as<ColpackResult>(), s_compute_);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipMemcpyAsync(h_pack_results_[slot].as(), d_pack_results_[slot].as(),
+                               (size_t)pack_n_[q] * sizeof(ColpackResult), hipMemcpyDeviceToHost, s_compute_));
+    }
     HIP_CHECK(hipEventRecord(merged_ev_[slot], s_compute_));
     if (sdma_stage) {
       std::lock_guard<std::mutex> g(mu_);
@@ -2073,6 +2215,14 @@ StepStats ShuffleJob::run_step(bool validate) {
   st.d2h_ms = step_d2h_ms_;
   st.bytes_in = st.records * kTeraRecordBytes;
   st.buffers = step_buffers_;
+  {
+    std::lock_guard<std::mutex> g(mu_);
+    st.d2h_bytes = step_d2h_bytes_;
+    st.packed_pieces = step_packed_;
+    st.raw_pieces = step_raw_;
+    st.unpack_ms = step_unpack_ms_;
+  }
+  if (deliver && st.bytes_in > 0) last_d2h_ratio_ = (double)st.d2h_bytes / (double)st.bytes_in;
   if (validate) {
     unsigned long long v[3];
     HIP_CHECK(hipMemcpy(v, vstats, sizeof(v), hipMemcpyDeviceToHost));

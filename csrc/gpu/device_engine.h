@@ -276,6 +276,10 @@ struct ShuffleConfig {
   // validate steps: also checksum every round's merged output right before its D2H (device) and as the
   // consumer threads receive it (host), per (round, reducer); costs a host hash of every record
   bool check_delivery = false;
+  // "auto" (on): merged records are bit-packed per column on the device before their D2H (colpack,
+  // codec/colpack.h) and unpacked by the consumer threads right before the sink; "off": sent as they
+  // are. UDA_DELIVERY_PACK=0 forces off.
+  std::string delivery_pack = "auto";
 };
 
 struct StepStats {
@@ -291,6 +295,10 @@ struct StepStats {
   int64_t bytes_sent = 0;      // bytes this rank sent to peers (excl. self)
   int64_t bytes_h2d = 0;       // spill tier: bytes streamed host -> device
   int64_t buffers = 0;         // sink invocations
+  int64_t d2h_bytes = 0;       // bytes the delivery copied over the link (packed pieces: their packed length)
+  int64_t packed_pieces = 0;   // delivery pieces sent bit-packed (colpack)
+  int64_t raw_pieces = 0;      // delivery pieces sent as they are
+  double unpack_ms = 0;        // host time the consumer threads spent unpacking (summed over consumers)
   int merge_passes = 0;
   bool validated = false;      // the checks below ran
   int64_t order_errors = -1;   // validate only
@@ -466,6 +474,26 @@ class ShuffleJob {
   hipStream_t s_stage_ = nullptr;  // disk tier, W == 1: H2D of the staging thread
   int64_t buf_records_ = 0;
   int64_t piece_bytes_ = 0;
+  // delivery bit-packing (cfg.delivery_pack): after a round's merge its output slot is packed piece by
+  // piece into the packed slot of the same parity; every piece has a fixed region there (its bound),
+  // and the per-piece lengths and flags reach the copy thread through a pinned table per slot
+  struct PackPiece {
+    int64_t src_off;  // bytes into the output slot
+    int64_t dst_off;  // bytes into the packed slot
+    int64_t nrec;
+  };
+  // the D2H pieces of a round in copy_loop's order (reducers with no records this round have none)
+  std::vector<PackPiece> round_pieces(const std::vector<int64_t>& group_recs) const;
+  bool pack_ = false;
+  std::vector<DeviceBuffer> packed_slots_;     // per slot
+  std::vector<DeviceBuffer> d_pack_pieces_;    // per round: ColpackPieceDesc[pack_n_[q]]
+  std::vector<int> pack_n_;
+  std::vector<int64_t> pack_max_nrec_;
+  DeviceBuffer d_pack_table_;
+  std::vector<DeviceBuffer> d_pack_results_;   // per slot: ColpackResult per piece
+  std::vector<PinnedBuffer> h_pack_results_;   // per slot, valid once merged_ev_[slot] has passed
+  int64_t ring_stride_ = 0;                    // bytes per pinned ring slot (>= piece_bytes_)
+  double last_d2h_ratio_ = -1;                 // last step: d2h_bytes / bytes_in
 
   // ---- delivery: copy thread -> pinned ring (SDMA) -> per-reducer consumer threads
   std::unique_ptr<SdmaEngine> sdma_;
@@ -484,6 +512,8 @@ class ShuffleJob {
     bool last;          // this reducer's final data: append EOF
     double issued_ms;
     int q;              // round of the bytes (check_delivery)
+    bool packed = false;  // the ring slot holds a colpack piece of `copied` bytes that unpacks to `bytes`
+    int64_t copied = 0;
   };
   std::mutex mu_;
   std::condition_variable cv_;
@@ -499,8 +529,11 @@ class ShuffleJob {
   int step_error_ = 0;
   std::string step_error_msg_;
   double step_d2h_ms_ = 0;
+  int64_t step_d2h_bytes_ = 0, step_packed_ = 0, step_raw_ = 0;
+  double step_unpack_ms_ = 0;
   SinkFn sink_;
   std::vector<std::unique_ptr<uint8_t[]>> eof_bufs_;  // per reducer: final chunk + EOF marker
+  std::vector<std::unique_ptr<uint8_t[]>> unpack_bufs_;  // per reducer: two staging buffers, alternating
 };
 
 // ncclUniqueId as bytes (rank 0 creates, others receive it out of band).

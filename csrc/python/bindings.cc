@@ -43,6 +43,8 @@
 #include "uda/topology.h"
 #include "uda/transport.h"
 #include "../gpu/hbm_ledger.h"
+#include "../gpu/kernels.h"
+#include "codec/colpack.h"
 #include <atomic>
 #include <thread>
 
@@ -72,6 +74,10 @@ py::dict stats_to_dict(const gpu::StepStats& s) {
   d["bytes_sent"] = s.bytes_sent;
   d["bytes_h2d"] = s.bytes_h2d;
   d["buffers"] = s.buffers;
+  d["d2h_bytes"] = s.d2h_bytes;
+  d["packed_pieces"] = s.packed_pieces;
+  d["raw_pieces"] = s.raw_pieces;
+  d["unpack_ms"] = s.unpack_ms;
   d["merge_passes"] = s.merge_passes;
   d["order_errors"] = s.order_errors;
   d["checksum"] = s.checksum;
@@ -115,6 +121,7 @@ gpu::ShuffleConfig config_from_dict(const py::dict& d) {
   get("replan", c.replan);
   get("map_sort", c.map_sort);
   get("check_delivery", c.check_delivery);
+  get("delivery_pack", c.delivery_pack);
   return c;
 }
 
@@ -332,6 +339,96 @@ PYBIND11_MODULE(_uda_native, m) {
     out.resize(n);
     return py::bytes(out);
   });
+  // colpack (codec/colpack.h): the host reference encoder and the consumers' decoder
+  m.def("colpack_header_bytes", [] { return (int64_t)kColpackHeaderBytes; });
+  m.def("colpack_have_bmi2", &colpack_have_bmi2);
+  m.def("colpack_encode", [](py::bytes b, int L, int64_t buf_records) {
+    std::string s = b;
+    if (L < 1 || L > kColpackMaxRecordBytes || s.empty() || s.size() % (size_t)L)
+      throw py::value_error("colpack_encode: need whole records of 1..256 bytes");
+    const int64_t nrec = (int64_t)s.size() / L;
+    std::string out((size_t)colpack_bound(L, nrec), '\0');
+    const int64_t n = colpack_encode((const uint8_t*)s.data(), nrec, L, buf_records, (uint8_t*)&out[0]);
+    out.resize((size_t)n);
+    return py::bytes(out);
+  }, py::arg("records"), py::arg("record_bytes"), py::arg("buf_records") = 1);
+  // path: "auto", "bmi2" or "scalar"; rows [row0, row0 + rows) (rows < 0: to the end). Raises ValueError for a
+  // piece whose header fails its checks, or that is marked raw.
+  m.def("colpack_decode", [](py::bytes b, int expect_L, int64_t expect_records, const std::string& path, int64_t row0,
+                             int64_t rows) {
+    std::string s = b;
+    ColpackPiece p;
+    const char* why = "";
+    if (!colpack_open((const uint8_t*)s.data(), (int64_t)s.size(), expect_L, expect_records, &p, &why))
+      throw py::value_error(std::string("colpack: ") + why);
+    if (!p.packed) throw py::value_error("colpack: raw piece");
+    if (rows < 0) rows = p.records - row0;
+    if (row0 < 0 || rows < 0 || row0 + rows > p.records) throw py::value_error("colpack: rows out of range");
+    std::string out((size_t)(rows * p.L), '\0');
+    if (path == "bmi2") {
+      if (!colpack_unpack_bmi2(p, row0, rows, (uint8_t*)&out[0])) throw std::runtime_error("no BMI2 on this CPU");
+    } else if (path == "scalar") {
+      colpack_unpack_scalar(p, row0, rows, (uint8_t*)&out[0]);
+    } else {
+      colpack_unpack(p, row0, rows, (uint8_t*)&out[0]);
+    }
+    return py::bytes(out);
+  }, py::arg("piece"), py::arg("expect_record_bytes") = 0, py::arg("expect_records") = 0, py::arg("path") = "auto",
+     py::arg("row0") = 0, py::arg("rows") = -1);
+  // The three device kernels over `pieces` (each a bytes object of whole records of record_bytes): returns
+  // per piece (the bytes the kernels wrote: header, rows, padding; packed flag; stride).
+  m.def("gpu_colpack_encode", [](const std::vector<std::string>& pieces, int L, int64_t buf_records, int device) {
+    if (L < 1 || L > kColpackMaxRecordBytes || pieces.empty()) throw py::value_error("gpu_colpack_encode: bad arguments");
+    std::vector<int64_t> src_off, dst_off, nrec;
+    int64_t src_bytes = 0, dst_bytes = 0, max_nrec = 0;
+    for (const auto& s : pieces) {
+      if (s.empty() || s.size() % (size_t)L) throw py::value_error("gpu_colpack_encode: need whole records");
+      src_off.push_back(src_bytes);
+      dst_off.push_back(dst_bytes);
+      nrec.push_back((int64_t)s.size() / L);
+      max_nrec = std::max(max_nrec, nrec.back());
+      src_bytes += ((int64_t)s.size() + 7) / 8 * 8;
+      dst_bytes += colpack_bound(L, nrec.back());
+    }
+    const int n = (int)pieces.size();
+    std::vector<gpu::ColpackResult> res((size_t)n);
+    std::vector<std::string> out((size_t)n);
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      gpu::DeviceBuffer dsrc, ddst, ddesc, dtab, dres;
+      dsrc.alloc((size_t)src_bytes);
+      ddst.alloc((size_t)dst_bytes);
+      ddesc.alloc((size_t)n * sizeof(gpu::ColpackPieceDesc));
+      dtab.alloc(gpu::colpack_table_bytes(n));
+      dres.alloc((size_t)n * sizeof(gpu::ColpackResult));
+      std::vector<gpu::ColpackPieceDesc> descs;
+      for (int i = 0; i < n; ++i) {
+        HIP_CHECK(hipMemcpy(dsrc.as<uint8_t>() + src_off[i], pieces[i].data(), pieces[i].size(), hipMemcpyHostToDevice));
+        descs.push_back(gpu::ColpackPieceDesc{dsrc.as<uint8_t>() + src_off[i], ddst.as<uint8_t>() + dst_off[i], nrec[i]});
+      }
+      HIP_CHECK(hipMemset(ddst.as(), 0xEE, (size_t)dst_bytes));  // whatever the kernels do not write shows
+      HIP_CHECK(hipMemcpy(ddesc.as(), descs.data(), descs.size() * sizeof(descs[0]), hipMemcpyHostToDevice));
+      hipStream_t s = nullptr;
+      HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      gpu::launch_colpack(ddesc.as<gpu::ColpackPieceDesc>(), n, max_nrec, L, buf_records, dtab.as<uint32_t>(),
+                          dres.as<gpu::ColpackResult>(), s);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipStreamSynchronize(s));
+      HIP_CHECK(hipStreamDestroy(s));
+      HIP_CHECK(hipMemcpy(res.data(), dres.as(), res.size() * sizeof(res[0]), hipMemcpyDeviceToHost));
+      for (int i = 0; i < n; ++i) {
+        if (res[(size_t)i].bytes < 0 || res[(size_t)i].bytes > colpack_bound(L, nrec[i]))
+          throw std::runtime_error("gpu_colpack_encode: a piece's length is outside its region");
+        out[(size_t)i].resize((size_t)res[(size_t)i].bytes);
+        HIP_CHECK(hipMemcpy(&out[(size_t)i][0], ddst.as<uint8_t>() + dst_off[i], out[(size_t)i].size(), hipMemcpyDeviceToHost));
+      }
+    }
+    py::list ret;
+    for (int i = 0; i < n; ++i)
+      ret.append(py::make_tuple(py::bytes(out[(size_t)i]), res[(size_t)i].packed != 0, (int64_t)res[(size_t)i].stride));
+    return ret;
+  }, py::arg("pieces"), py::arg("record_bytes"), py::arg("buf_records") = 1, py::arg("device") = 0);
   m.def("codec_from_class", [](const std::string& c) {
     bool unsup = false;
     int v = (int)codec_from_class(c, &unsup);

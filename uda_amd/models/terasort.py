@@ -55,6 +55,7 @@ class TeraSortConfig:
     replan: bool = False                # every step recomputes the cell splits and exchanges the counts
     map_sort: bool = False              # setup: unsorted map input sorted on the device (F8 radix sort)
     check_delivery: bool = False        # validate steps: checksum every round output before its D2H and as received
+    delivery_pack: str = "auto"         # "auto": bit-pack merged records per column before their D2H; "off"
     exchange: str = "ipc"               # world > 1: "ipc" (shared-memory control + hipIpc pulls) or "rccl"
 
 
@@ -73,7 +74,8 @@ class TeraSortShuffle:
             d2h_piece_bytes=cfg.d2h_piece_bytes, pinned_slots=cfg.pinned_slots,
             d2h_engines=cfg.d2h_engines, d2h=cfg.d2h, deliver_host=cfg.deliver_host,
             validate=cfg.validate, store=cfg.store, local_dirs=cfg.local_dirs, replan=cfg.replan,
-            map_sort=cfg.map_sort, check_delivery=cfg.check_delivery))
+            map_sort=cfg.map_sort, check_delivery=cfg.check_delivery,
+        delivery_pack=cfg.delivery_pack))
         self.sink = n.J2CSink(cfg.reducers, cfg.kv_buf_bytes)
         self.sampler = None                 # sample_outputs(): a StreamSampler beside the sink
         self.sample_index = []
@@ -250,7 +252,8 @@ def make_local_group(world: int, cfg: TeraSortConfig, device: int = 0, group: st
         kv_buf_bytes=cfg.kv_buf_bytes, d2h_piece_bytes=cfg.d2h_piece_bytes, pinned_slots=cfg.pinned_slots,
         d2h_engines=cfg.d2h_engines, d2h=cfg.d2h, deliver_host=cfg.deliver_host, validate=cfg.validate,
         local_group=group, store=cfg.store, local_dirs=cfg.local_dirs, replan=cfg.replan,
-        map_sort=cfg.map_sort, check_delivery=cfg.check_delivery))
+        map_sort=cfg.map_sort, check_delivery=cfg.check_delivery,
+        delivery_pack=cfg.delivery_pack))
         for r in range(world)]
     for j in jobs:
         j.init_local()
