@@ -770,6 +770,7 @@ ShuffleJob::ShuffleJob(const ShuffleConfig& cfg) : cfg_(cfg) {
     throw std::runtime_error("unknown store tier " + cfg_.store);
   if (cfg_.delivery_pack != "auto" && cfg_.delivery_pack != "off")
     throw std::runtime_error("ShuffleJob: delivery_pack must be auto or off");
+  check_delivery_order(cfg_.delivery_order);
   pack_ = cfg_.deliver_host && cfg_.delivery_pack == "auto";
   if (const char* e = std::getenv("UDA_DELIVERY_PACK"))
     if (std::atoi(e) == 0) pack_ = false;
@@ -798,6 +799,8 @@ ShuffleJob::ShuffleJob(const ShuffleConfig& cfg) : cfg_(cfg) {
   merged_ev_.resize(kSlots);
   comm_ev_.resize(kSlots);
   sent_ev_.resize(2);
+  early_ev_.resize(kSlots);
+  for (auto& e : early_ev_) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   for (auto& e : merged_ev_) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   for (auto& e : comm_ev_) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   for (auto& e : sent_ev_) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -814,6 +817,7 @@ ShuffleJob::~ShuffleJob() {
     if (t.joinable()) t.join();
   (void)hipDeviceSynchronize();
   for (auto e : merged_ev_) (void)hipEventDestroy(e);
+  for (auto e : early_ev_) (void)hipEventDestroy(e);
   if (s_stage_) (void)hipStreamDestroy(s_stage_);
   for (auto e : comm_ev_) (void)hipEventDestroy(e);
   for (auto e : sent_ev_) (void)hipEventDestroy(e);
@@ -854,7 +858,7 @@ void ShuffleJob::init_ipc(const std::string& name) {
 std::string ShuffleJob::delivery_name() const {
   if (!cfg_.deliver_host) return "none";
   std::string name = sdma_ ? sdma_->describe() : "hip[numa=" + std::to_string(device_numa_node(cfg_.device)) + "]";
-  name += " ring=" + ring_numa_;
+  name += " ring=" + ring_numa_ + " order=" + cfg_.delivery_order;
   if (!pack_) return name + " pack=off";
   name += " pack=colbits";
   if (last_d2h_ratio_ >= 0) {  // the last step's d2h_bytes / bytes_in
@@ -867,19 +871,44 @@ std::string ShuffleJob::delivery_name() const {
 
 std::vector<ShuffleJob::PackPiece> ShuffleJob::round_pieces(const std::vector<int64_t>& group_recs) const {
   std::vector<PackPiece> v;
-  int64_t goff = 0, doff = 0;
-  for (int i = 0; i < R_; ++i) {
-    const int64_t bytes = group_recs[i] * kTeraRecordBytes;
-    for (int64_t off = 0; off < bytes;) {
-      const int64_t len = std::min(piece_bytes_, bytes - off);
-      const int64_t nrec = len / kTeraRecordBytes;
-      v.push_back(PackPiece{goff + off, doff, nrec});
-      doff += colpack_bound(kTeraRecordBytes, nrec);
-      off += len;
-    }
-    goff += bytes;
+  int64_t doff = 0;
+  for (const DeliveryPiece& dp : delivery_schedule(group_recs, piece_bytes_, "reducer", kTeraRecordBytes)) {
+    const int64_t nrec = dp.len / kTeraRecordBytes;
+    v.push_back(PackPiece{dp.src_off, doff, nrec});
+    doff += colpack_bound(kTeraRecordBytes, nrec);
   }
   return v;
+}
+
+void ShuffleJob::note_issue(int k, double now) {
+  if (first_issue_ms_ < 0) first_issue_ms_ = now;
+  if (flying_ == 0 && idle_since_ms_ >= 0) step_link_idle_ms_ += now - idle_since_ms_;
+  slot_flying_[k] = true;
+  ++flying_;
+}
+
+void ShuffleJob::note_landing(int k, double now) {
+  if (!slot_flying_[k]) return;  // another waiter saw it first
+  slot_flying_[k] = false;
+  last_landing_ms_ = now;
+  if (--flying_ == 0) idle_since_ms_ = now;
+}
+
+void ShuffleJob::poll_landings() {
+  if (flying_ == 0) return;
+  for (int k = 0; k < (int)slot_flying_.size(); ++k) {
+    if (!slot_flying_[k]) continue;
+    // a copy error (negative signal, failed event) is left to the piece's waiter, which throws
+    bool done;
+    if (sdma_) {
+      done = hsa_signal_load_relaxed(piece_sig_[k]) == 0;
+    } else {
+      const hipError_t e = hipEventQuery(piece_ev_[k]);
+      done = e == hipSuccess;
+      if (e == hipErrorNotReady) (void)hipGetLastError();  // not an error: not left for a later HIP_PENDING
+    }
+    if (done) note_landing(k, now_ms());
+  }
 }
 
 void ShuffleJob::generate() {
@@ -1314,6 +1343,7 @@ void ShuffleJob::compute_plans() {
   h_pack_results_.clear();
   pack_n_.assign(Q_, 0);
   pack_max_nrec_.assign(Q_, 0);
+  pack_early_.assign(Q_, 0);
   if (pack_) {
     int64_t packed_bytes = 64;
     int max_pieces = 1;
@@ -1340,10 +1370,18 @@ void ShuffleJob::compute_plans() {
     d_pack_pieces_.resize(Q_);
     for (int q = 0; q < Q_; ++q) {
       if (pieces[q].empty()) continue;
+      // descriptors (and with them the results) in issue order; a piece's packed region stays where the
+      // reducer-major list put it. Wave order: the first wave is packed by a launch of its own (run_step).
       std::vector<ColpackPieceDesc> v;
-      for (const PackPiece& pc : pieces[q])
+      int wave0 = 0;
+      for (const DeliveryPiece& dp :
+           delivery_schedule(plans_[q].group_recs, piece_bytes_, cfg_.delivery_order, kTeraRecordBytes)) {
+        const PackPiece& pc = pieces[q][(size_t)dp.pack_index];
         v.push_back(ColpackPieceDesc{out_slots_[q % kSlots].as<uint8_t>() + pc.src_off,
                                      packed_slots_[q % kSlots].as<uint8_t>() + pc.dst_off, pc.nrec});
+      }
+      for (int64_t g : plans_[q].group_recs) wave0 += g > 0 ? 1 : 0;
+      if (cfg_.delivery_order == "wave" && wave0 < pack_n_[q]) pack_early_[q] = wave0;
       d_pack_pieces_[q].alloc(v.size() * sizeof(ColpackPieceDesc));
       HIP_CHECK(hipMemcpy(d_pack_pieces_[q].as(), v.data(), v.size() * sizeof(ColpackPieceDesc), hipMemcpyHostToDevice));
     }
@@ -1506,6 +1544,8 @@ void ShuffleJob::plan() {
     for (size_t o = 0; o < ring_bytes; o += 4096) ring_[o] = 0;
     ring_numa_ = numa_residency(ring_);
     pinned_free_.assign(cfg_.pinned_slots, true);
+    slot_flying_.assign(cfg_.pinned_slots, false);
+    flying_ = 0;
     items_.assign(R_, {});
     eof_bufs_.clear();
     for (int i = 0; i < R_; ++i) eof_bufs_.emplace_back(new uint8_t[(size_t)cfg_.kv_buf_bytes + 16]);
@@ -1525,7 +1565,8 @@ void ShuffleJob::wait_exchange_ok() {
   if (exchange_) exchange_->check();
 }
 
-// Copy thread: merged rounds -> D2H pieces in the pinned ring, per reducer, in round order.
+// Copy thread: merged rounds -> D2H pieces in the pinned ring, in round order; within a round in
+// delivery_schedule()'s order (cfg.delivery_order).
 void ShuffleJob::copy_loop() {
   try {
     bind_thread_to_cpus(device_consumer_cpus(cfg_.device));
@@ -1539,7 +1580,8 @@ void ShuffleJob::copy_loop() {
         r = std::move(round_q_.front());
         round_q_.pop_front();
       }
-      HIP_CHECK(hipEventSynchronize(merged_ev_[r.slot]));
+      // merged, and packed as far as the first pieces need: the whole round, or its first wave (r.early)
+      HIP_CHECK(hipEventSynchronize(r.early > 0 ? early_ev_[r.slot] : merged_ev_[r.slot]));
       const uint8_t* src = out_slots_[r.slot].as<uint8_t>();
       const bool last_round = (r.q == Q_ - 1);
       bool check;
@@ -1569,74 +1611,86 @@ void ShuffleJob::copy_loop() {
         for (int i = 0; i < R_; ++i) pre_d2h_ck_[(size_t)r.q * R_ + i] = ck[i];
       }
       std::vector<int> used;
-      int64_t goff = 0;
-      // packed rounds: piece p of round_pieces(), its length and flag as the plan kernel wrote them
+      // packed rounds: a piece's region is that of round_pieces()[pack_index]; its length and flag as the plan
+      // kernel wrote them are in the results table at its place in the issue order
       const std::vector<PackPiece> ppieces = pack_ ? round_pieces(r.group_recs) : std::vector<PackPiece>();
       const ColpackResult* pres = pack_ ? h_pack_results_[r.slot].as<ColpackResult>() : nullptr;
-      size_t pi = 0;
-      for (int i = 0; i < R_; ++i) {
-        const int64_t bytes = r.group_recs[i] * kTeraRecordBytes;
-        if (bytes == 0 && last_round) {
-          {
-            std::lock_guard<std::mutex> g(mu_);
-            items_[i].push_back(Item{-1, 0, true, now_ms(), r.q});
-          }
-          cv_.notify_all();
-        }
-        for (int64_t off = 0; off < bytes;) {
-          const int64_t len = std::min(piece_bytes_, bytes - off);
-          int k = -1;
-          {
-            std::unique_lock<std::mutex> lk(mu_);
-            cv_.wait(lk, [&] {
-              if (stop_) return true;
-              for (bool f : pinned_free_)
-                if (f) return true;
-              return false;
-            });
-            if (stop_) return;
-            for (int x = 0; x < (int)pinned_free_.size(); ++x)
-              if (pinned_free_[x]) {
-                k = x;
-                break;
-              }
-            pinned_free_[k] = false;
-          }
-          uint8_t* dst = ring_ + (int64_t)k * ring_stride_;
-          const uint8_t* from = src + goff + off;
-          int64_t copy_len = len;
-          bool packed = false;
-          if (pack_) {
-            if (pi >= ppieces.size() || ppieces[pi].src_off != goff + off || ppieces[pi].nrec * kTeraRecordBytes != len)
-              throw std::runtime_error("delivery_pack: piece list out of step with the copy loop");
-            const ColpackResult pr = pres[pi];
-            if (pr.packed) {
-              if (pr.bytes < (int64_t)kColpackHeaderBytes || pr.bytes > colpack_bound(kTeraRecordBytes, ppieces[pi].nrec))
-                throw std::runtime_error("delivery_pack: packed length outside the piece's region");
-              packed = true;
-              copy_len = pr.bytes;
-              from = packed_slots_[r.slot].as<uint8_t>() + ppieces[pi].dst_off;
+      if (last_round) {  // a reducer without records in the last round: its EOF travels alone
+        bool any = false;
+        {
+          std::lock_guard<std::mutex> g(mu_);
+          for (int i = 0; i < R_; ++i)
+            if (r.group_recs[i] == 0) {
+              items_[i].push_back(Item{-1, 0, true, now_ms(), r.q});
+              any = true;
             }
-            ++pi;
-          }
-          if (sdma_) {
-            SdmaEngine::arm(piece_sig_[k], sdma_->parts((size_t)copy_len, cfg_.d2h_engines));
-            sdma_->copy_d2h(dst, from, (size_t)copy_len, piece_sig_[k], cfg_.d2h_engines);
-          } else {
-            HIP_CHECK(hipMemcpyAsync(dst, from, (size_t)copy_len, hipMemcpyDeviceToHost, s_copy_));
-            HIP_CHECK(hipEventRecord(piece_ev_[k], s_copy_));
-          }
-          off += len;
-          used.push_back(k);
-          {
-            std::lock_guard<std::mutex> g(mu_);
-            items_[i].push_back(Item{k, len, last_round && off >= bytes, now_ms(), r.q, packed, copy_len});
-            step_d2h_bytes_ += copy_len;
-            ++(packed ? step_packed_ : step_raw_);
-          }
-          cv_.notify_all();
         }
-        goff += bytes;
+        if (any) cv_.notify_all();
+      }
+      // Pieces go out in schedule order and take their ring slots in that order: every held slot belongs
+      // to an issued piece whose consumer reaches it without needing another slot, so no order can deadlock.
+      int issued = 0;
+      for (const DeliveryPiece& dp :
+           delivery_schedule(r.group_recs, piece_bytes_, cfg_.delivery_order, kTeraRecordBytes)) {
+        if (r.early > 0 && issued == r.early) HIP_CHECK(hipEventSynchronize(merged_ev_[r.slot]));  // the rest is packed
+        int k = -1;
+        {
+          std::unique_lock<std::mutex> lk(mu_);
+          auto have_slot = [&] {
+            if (stop_) return true;
+            for (bool f : pinned_free_)
+              if (f) return true;
+            return false;
+          };
+          if (!have_slot()) {  // ring full: meanwhile, see the copies in flight land (link_idle_ms)
+            const double tw = now_ms();
+            while (!cv_.wait_for(lk, std::chrono::microseconds(200), have_slot)) poll_landings();
+            step_slot_wait_ms_ += now_ms() - tw;
+          }
+          if (stop_) return;
+          for (int x = 0; x < (int)pinned_free_.size(); ++x)
+            if (pinned_free_[x]) {
+              k = x;
+              break;
+            }
+          pinned_free_[k] = false;
+        }
+        uint8_t* dst = ring_ + (int64_t)k * ring_stride_;
+        const uint8_t* from = src + dp.src_off;
+        int64_t copy_len = dp.len;
+        bool packed = false;
+        if (pack_) {
+          const size_t pi = (size_t)dp.pack_index;
+          if (pi >= ppieces.size() || (size_t)issued >= ppieces.size() || ppieces[pi].src_off != dp.src_off ||
+              ppieces[pi].nrec * kTeraRecordBytes != dp.len)
+            throw std::runtime_error("delivery_pack: piece list out of step with the copy loop");
+          const ColpackResult pr = pres[issued];
+          if (pr.packed) {
+            if (pr.bytes < (int64_t)kColpackHeaderBytes || pr.bytes > colpack_bound(kTeraRecordBytes, ppieces[pi].nrec))
+              throw std::runtime_error("delivery_pack: packed length outside the piece's region");
+            packed = true;
+            copy_len = pr.bytes;
+            from = packed_slots_[r.slot].as<uint8_t>() + ppieces[pi].dst_off;
+          }
+        }
+        if (sdma_) {
+          SdmaEngine::arm(piece_sig_[k], sdma_->parts((size_t)copy_len, cfg_.d2h_engines));
+          sdma_->copy_d2h(dst, from, (size_t)copy_len, piece_sig_[k], cfg_.d2h_engines);
+        } else {
+          HIP_CHECK(hipMemcpyAsync(dst, from, (size_t)copy_len, hipMemcpyDeviceToHost, s_copy_));
+          HIP_CHECK(hipEventRecord(piece_ev_[k], s_copy_));
+        }
+        used.push_back(k);
+        ++issued;
+        {
+          std::lock_guard<std::mutex> g(mu_);
+          const double now = now_ms();
+          note_issue(k, now);
+          items_[dp.reducer].push_back(Item{k, dp.len, last_round && dp.last_of_reducer, now, r.q, packed, copy_len});
+          step_d2h_bytes_ += copy_len;
+          ++(packed ? step_packed_ : step_raw_);
+        }
+        cv_.notify_all();
       }
       // the output slot is free once every piece of this round has landed in the ring
       for (int k : used) {
@@ -1644,6 +1698,8 @@ void ShuffleJob::copy_loop() {
           SdmaEngine::wait(piece_sig_[k]);
         else
           HIP_CHECK(hipEventSynchronize(piece_ev_[k]));
+        std::lock_guard<std::mutex> g(mu_);
+        note_landing(k, now_ms());
       }
       {
         std::lock_guard<std::mutex> g(mu_);
@@ -1691,7 +1747,12 @@ void ShuffleJob::consume_loop(int i) {
           SdmaEngine::wait(piece_sig_[it.pslot]);
         else
           HIP_CHECK(hipEventSynchronize(piece_ev_[it.pslot]));
-        waited = now_ms() - it.issued_ms;
+        {
+          std::lock_guard<std::mutex> g(mu_);
+          const double now = now_ms();
+          note_landing(it.pslot, now);
+          waited = now - it.issued_ms;
+        }
         const uint8_t* base = ring_ + (int64_t)it.pslot * ring_stride_;
         ColpackPiece pp;
         if (it.packed) {  // a header that fails its checks fails the step and is never unpacked
@@ -1752,7 +1813,7 @@ void ShuffleJob::consume_loop(int i) {
         step_d2h_ms_ += waited;
         step_unpack_ms_ += unpack_ms;
         if (err && !step_error_) step_error_ = err;
-        if (it.last) ++eof_count_;
+        if (it.last && ++eof_count_ == R_) eof_done_ms_ = now_ms();
       }
       cv_.notify_all();
     }
@@ -1869,6 +1930,9 @@ StepStats ShuffleJob::run_step(bool validate) {
     step_d2h_ms_ = 0;
     step_d2h_bytes_ = step_packed_ = step_raw_ = 0;
     step_unpack_ms_ = 0;
+    step_t0_ms_ = t0;
+    first_issue_ms_ = last_landing_ms_ = idle_since_ms_ = eof_done_ms_ = -1;
+    step_link_idle_ms_ = step_slot_wait_ms_ = 0;
     step_check_delivery_ = validate && cfg_.check_delivery && deliver;
     pre_d2h_ck_.assign((size_t)Q_ * R_, 0);
     delivered_ck_.assign((size_t)Q_ * R_, 0);
@@ -2161,11 +2225,21 @@ StepStats ShuffleJob::run_step(bool validate) {
     }
     HIP_CHECK(hipEventRecord(ev[4 * q + 3], s_compute_));
     if (pack_ && deliver && pack_n_[q] > 0) {  // bit-pack the round's D2H pieces; lengths and flags to the copy thread
-      launch_colpack(d_pack_pieces_[q].as<ColpackPieceDesc>(), pack_n_[q], pack_max_nrec_[q], kTeraRecordBytes,
-                     buf_records_, d_pack_table_.as<uint32_t>(), d_pack_results_[slot].as<ColpackResult>(), s_compute_);
-      HIP_CHECK(hipGetLastError());
-      HIP_CHECK(hipMemcpyAsync(h_pack_results_[slot].as(), d_pack_results_[slot].as(),
-                               (size_t)pack_n_[q] * sizeof(ColpackResult), hipMemcpyDeviceToHost, s_compute_));
+      // pieces [a, b) of the round's issue-ordered descriptors: pack them, results to the pinned table
+      auto pack_range = [&](int a, int b) {
+        launch_colpack(d_pack_pieces_[q].as<ColpackPieceDesc>() + a, b - a, pack_max_nrec_[q], kTeraRecordBytes,
+                       buf_records_, d_pack_table_.as<uint32_t>(), d_pack_results_[slot].as<ColpackResult>() + a,
+                       s_compute_);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(h_pack_results_[slot].as<ColpackResult>() + a,
+                                 d_pack_results_[slot].as<ColpackResult>() + a, (size_t)(b - a) * sizeof(ColpackResult),
+                                 hipMemcpyDeviceToHost, s_compute_));
+      };
+      if (pack_early_[q] > 0) {  // the first wave leaves while the rest of the round is packed
+        pack_range(0, pack_early_[q]);
+        HIP_CHECK(hipEventRecord(early_ev_[slot], s_compute_));
+      }
+      pack_range(pack_early_[q], pack_n_[q]);
     }
     HIP_CHECK(hipEventRecord(merged_ev_[slot], s_compute_));
     if (sdma_stage) {
@@ -2177,7 +2251,7 @@ StepStats ShuffleJob::run_step(bool validate) {
     if (deliver) {
       {
         std::lock_guard<std::mutex> g(mu_);
-        round_q_.push_back(RoundOut{q, slot, rp.group_recs});
+        round_q_.push_back(RoundOut{q, slot, rp.group_recs, pack_early_[q]});
       }
       cv_.notify_all();
     }
@@ -2221,6 +2295,12 @@ StepStats ShuffleJob::run_step(bool validate) {
     st.packed_pieces = step_packed_;
     st.raw_pieces = step_raw_;
     st.unpack_ms = step_unpack_ms_;
+    st.slot_wait_ms = step_slot_wait_ms_;
+    if (first_issue_ms_ >= 0) {  // every piece has landed and every EOF is out by now
+      st.lead_in_ms = first_issue_ms_ - step_t0_ms_;
+      st.link_idle_ms = step_link_idle_ms_;
+      if (eof_done_ms_ >= last_landing_ms_) st.tail_ms = eof_done_ms_ - last_landing_ms_;
+    }
   }
   if (deliver && st.bytes_in > 0) last_d2h_ratio_ = (double)st.d2h_bytes / (double)st.bytes_in;
   if (validate) {

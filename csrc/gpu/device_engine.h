@@ -38,6 +38,7 @@
 #include <thread>
 #include <vector>
 
+#include "delivery_schedule.h"
 #include "exchange.h"
 #include "kernels.h"
 #include "disk_store.h"
@@ -280,6 +281,10 @@ struct ShuffleConfig {
   // codec/colpack.h) and unpacked by the consumer threads right before the sink; "off": sent as they
   // are. UDA_DELIVERY_PACK=0 forces off.
   std::string delivery_pack = "auto";
+  // order the copy thread issues a round's D2H pieces in (delivery_schedule.h): "wave" (piece 0 of every
+  // reducer, then piece 1 of every reducer, ...: every consumer drains at once) or "reducer" (all pieces
+  // of reducer 0, then of reducer 1, ...)
+  std::string delivery_order = "wave";
 };
 
 struct StepStats {
@@ -299,6 +304,12 @@ struct StepStats {
   int64_t packed_pieces = 0;   // delivery pieces sent bit-packed (colpack)
   int64_t raw_pieces = 0;      // delivery pieces sent as they are
   double unpack_ms = 0;        // host time the consumer threads spent unpacking (summed over consumers)
+  // link occupancy of the delivery, from the copy thread's issues and the landings seen by whoever waits on
+  // a piece's signal or event; lead_in_ms + link_idle_ms + tail_ms <= wall_ms
+  double lead_in_ms = 0;       // step start to the first piece issued
+  double link_idle_ms = 0;     // between the first issue and the last landing: time with no copy in flight
+  double tail_ms = 0;          // last landing to the last reducer's EOF
+  double slot_wait_ms = 0;     // time the copy thread waited for a free pinned slot
   int merge_passes = 0;
   bool validated = false;      // the checks below ran
   int64_t order_errors = -1;   // validate only
@@ -482,16 +493,23 @@ class ShuffleJob {
     int64_t dst_off;  // bytes into the packed slot
     int64_t nrec;
   };
-  // the D2H pieces of a round in copy_loop's order (reducers with no records this round have none)
+  // the D2H pieces of a round, reducer-major: delivery_schedule()'s pack_index numbers them (reducers with
+  // no records this round have none)
   std::vector<PackPiece> round_pieces(const std::vector<int64_t>& group_recs) const;
   bool pack_ = false;
   std::vector<DeviceBuffer> packed_slots_;     // per slot
-  std::vector<DeviceBuffer> d_pack_pieces_;    // per round: ColpackPieceDesc[pack_n_[q]]
+  std::vector<DeviceBuffer> d_pack_pieces_;    // per round: ColpackPieceDesc[pack_n_[q]], in issue order
   std::vector<int> pack_n_;
+  // per round, wave order: its first pack_early_[q] pieces (the first wave) are packed by a launch of their
+  // own, early_ev_[slot] marks their results in the pinned table; 0: one launch for the whole round
+  std::vector<int> pack_early_;
+  std::vector<hipEvent_t> early_ev_;           // per slot
   std::vector<int64_t> pack_max_nrec_;
   DeviceBuffer d_pack_table_;
   std::vector<DeviceBuffer> d_pack_results_;   // per slot: ColpackResult per piece
-  std::vector<PinnedBuffer> h_pack_results_;   // per slot, valid once merged_ev_[slot] has passed
+  // per slot, a round's results in issue order: the first pack_early_[q] valid once early_ev_[slot] has
+  // passed, all of them once merged_ev_[slot] has
+  std::vector<PinnedBuffer> h_pack_results_;
   int64_t ring_stride_ = 0;                    // bytes per pinned ring slot (>= piece_bytes_)
   double last_d2h_ratio_ = -1;                 // last step: d2h_bytes / bytes_in
 
@@ -505,6 +523,7 @@ class ShuffleJob {
     int q;
     int slot;
     std::vector<int64_t> group_recs;
+    int early = 0;      // pack_early_[q]
   };
   struct Item {
     int pslot;          // pinned slot, -1 for an EOF-only item
@@ -531,6 +550,15 @@ class ShuffleJob {
   double step_d2h_ms_ = 0;
   int64_t step_d2h_bytes_ = 0, step_packed_ = 0, step_raw_ = 0;
   double step_unpack_ms_ = 0;
+  // link occupancy (StepStats lead_in_ms ...), all under mu_. A piece is in flight from its issue until
+  // someone sees its signal or event complete; slot_flying_[k]: ring slot k holds such a piece.
+  std::vector<bool> slot_flying_;
+  int flying_ = 0;
+  double step_t0_ms_ = 0, first_issue_ms_ = -1, last_landing_ms_ = -1, idle_since_ms_ = -1, eof_done_ms_ = -1;
+  double step_link_idle_ms_ = 0, step_slot_wait_ms_ = 0;
+  void note_issue(int k, double now);      // mu_ held
+  void note_landing(int k, double now);    // mu_ held
+  void poll_landings();                    // mu_ held: pieces whose copy is done but nobody has waited for yet
   SinkFn sink_;
   std::vector<std::unique_ptr<uint8_t[]>> eof_bufs_;  // per reducer: final chunk + EOF marker
   std::vector<std::unique_ptr<uint8_t[]>> unpack_bufs_;  // per reducer: two staging buffers, alternating

@@ -78,6 +78,10 @@ py::dict stats_to_dict(const gpu::StepStats& s) {
   d["packed_pieces"] = s.packed_pieces;
   d["raw_pieces"] = s.raw_pieces;
   d["unpack_ms"] = s.unpack_ms;
+  d["lead_in_ms"] = s.lead_in_ms;
+  d["link_idle_ms"] = s.link_idle_ms;
+  d["tail_ms"] = s.tail_ms;
+  d["slot_wait_ms"] = s.slot_wait_ms;
   d["merge_passes"] = s.merge_passes;
   d["order_errors"] = s.order_errors;
   d["checksum"] = s.checksum;
@@ -122,6 +126,7 @@ gpu::ShuffleConfig config_from_dict(const py::dict& d) {
   get("map_sort", c.map_sort);
   get("check_delivery", c.check_delivery);
   get("delivery_pack", c.delivery_pack);
+  get("delivery_order", c.delivery_order);
   return c;
 }
 
@@ -339,6 +344,23 @@ PYBIND11_MODULE(_uda_native, m) {
     out.resize(n);
     return py::bytes(out);
   });
+  // The D2H pieces of a delivery round in the copy thread's issue order (gpu/delivery_schedule.h):
+  // dicts of reducer, src_off, len, pack_index, last_of_reducer. ValueError for an unknown order.
+  m.def("delivery_schedule", [](const std::vector<int64_t>& group_recs, int64_t piece_bytes, const std::string& order,
+                                int64_t record_bytes) {
+    if (order != "wave" && order != "reducer") throw py::value_error("delivery_order must be wave or reducer");
+    py::list out;
+    for (const gpu::DeliveryPiece& p : gpu::delivery_schedule(group_recs, piece_bytes, order, record_bytes)) {
+      py::dict d;
+      d["reducer"] = p.reducer;
+      d["src_off"] = p.src_off;
+      d["len"] = p.len;
+      d["pack_index"] = p.pack_index;
+      d["last_of_reducer"] = p.last_of_reducer;
+      out.append(d);
+    }
+    return out;
+  }, py::arg("group_recs"), py::arg("piece_bytes"), py::arg("order") = "wave", py::arg("record_bytes") = 104);
   // colpack (codec/colpack.h): the host reference encoder and the consumers' decoder
   m.def("colpack_header_bytes", [] { return (int64_t)kColpackHeaderBytes; });
   m.def("colpack_have_bmi2", &colpack_have_bmi2);

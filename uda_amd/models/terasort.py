@@ -56,6 +56,7 @@ class TeraSortConfig:
     map_sort: bool = False              # setup: unsorted map input sorted on the device (F8 radix sort)
     check_delivery: bool = False        # validate steps: checksum every round output before its D2H and as received
     delivery_pack: str = "auto"         # "auto": bit-pack merged records per column before their D2H; "off"
+    delivery_order: str = "wave"        # a round's D2H pieces: "wave" (piece k of every reducer in turn) or "reducer"
     exchange: str = "ipc"               # world > 1: "ipc" (shared-memory control + hipIpc pulls) or "rccl"
 
 
@@ -75,7 +76,7 @@ class TeraSortShuffle:
             d2h_engines=cfg.d2h_engines, d2h=cfg.d2h, deliver_host=cfg.deliver_host,
             validate=cfg.validate, store=cfg.store, local_dirs=cfg.local_dirs, replan=cfg.replan,
             map_sort=cfg.map_sort, check_delivery=cfg.check_delivery,
-        delivery_pack=cfg.delivery_pack))
+            delivery_pack=cfg.delivery_pack, delivery_order=cfg.delivery_order))
         self.sink = n.J2CSink(cfg.reducers, cfg.kv_buf_bytes)
         self.sampler = None                 # sample_outputs(): a StreamSampler beside the sink
         self.sample_index = []
@@ -253,7 +254,7 @@ def make_local_group(world: int, cfg: TeraSortConfig, device: int = 0, group: st
         d2h_engines=cfg.d2h_engines, d2h=cfg.d2h, deliver_host=cfg.deliver_host, validate=cfg.validate,
         local_group=group, store=cfg.store, local_dirs=cfg.local_dirs, replan=cfg.replan,
         map_sort=cfg.map_sort, check_delivery=cfg.check_delivery,
-        delivery_pack=cfg.delivery_pack))
+        delivery_pack=cfg.delivery_pack, delivery_order=cfg.delivery_order))
         for r in range(world)]
     for j in jobs:
         j.init_local()
