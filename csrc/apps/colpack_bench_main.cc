@@ -4,7 +4,10 @@
 // staging buffer; "unpack+copy" also copies every buffer into a KVBuf as the J2C sink does, and "copy"
 // is that memcpy alone from the unpacked records. Rates are in unpacked bytes per second per thread.
 //
-//   uda_colpack_bench [--threads N] [--mib M] [--reps R] [--scalar]
+//   uda_colpack_bench [--threads N] [--mib M] [--reps R] [--scalar] [--v2]
+//
+// --v2: the piece is a version 2 piece (key differences of the 10-byte key, bit-contiguous rows) of
+// sorted records whose keys step as a flagship piece's do (differences of up to 54 bits).
 //
 // stdout: one JSON line.
 #include <chrono>
@@ -31,12 +34,12 @@ uint64_t splitmix(uint64_t& s) {
 }
 
 // [0x0B 0x5B 0x0A] key[10] [0x5A] value[90]: ascending keys in a narrow range, values 'A'..'Z'
-void fill(std::vector<uint8_t>& v, int64_t n, uint64_t seed) {
+void fill(std::vector<uint8_t>& v, int64_t n, uint64_t seed, uint64_t step_mask = 0xFFFFFF) {
   uint64_t key = seed << 40;
   for (int64_t r = 0; r < n; ++r) {
     uint8_t* p = v.data() + r * 104;
     p[0] = 0x0B, p[1] = 0x5B, p[2] = 0x0A, p[13] = 0x5A;
-    key += splitmix(seed) & 0xFFFFFF;
+    key += splitmix(seed) & step_mask;
     for (int b = 0; b < 8; ++b) p[3 + b] = (uint8_t)(key >> (56 - 8 * b));
     const uint64_t t = splitmix(seed);
     p[11] = (uint8_t)t, p[12] = (uint8_t)(t >> 8);
@@ -54,15 +57,16 @@ struct Result {
 int main(int argc, char** argv) {
   int threads = 1, reps = 3;
   int64_t mib = 128;
-  bool scalar = false;
+  bool scalar = false, v2 = false;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--threads" && i + 1 < argc) threads = std::atoi(argv[++i]);
     else if (a == "--mib" && i + 1 < argc) mib = std::atoll(argv[++i]);
     else if (a == "--reps" && i + 1 < argc) reps = std::atoi(argv[++i]);
     else if (a == "--scalar") scalar = true;
+    else if (a == "--v2") v2 = true;
     else {
-      std::fprintf(stderr, "usage: uda_colpack_bench [--threads N] [--mib M] [--reps R] [--scalar]\n");
+      std::fprintf(stderr, "usage: uda_colpack_bench [--threads N] [--mib M] [--reps R] [--scalar] [--v2]\n");
       return 2;
     }
   }
@@ -75,11 +79,13 @@ int main(int argc, char** argv) {
   for (int t = 0; t < threads; ++t)
     thr.emplace_back([&, t] {
       std::vector<uint8_t> raw((size_t)(n * 104));
-      fill(raw, n, 1234567 + (uint64_t)t);
-      std::vector<uint8_t> piece((size_t)uda::colpack_bound(104, n));
-      const int64_t len = uda::colpack_encode(raw.data(), n, 104, buf_records, piece.data());
+      // --v2: the top 8 key bytes step by up to 2^38, the low two are random: differences below 2^54
+      fill(raw, n, 1234567 + (uint64_t)t, v2 ? (1ull << 38) - 1 : 0xFFFFFF);
+      std::vector<uint8_t> piece((size_t)(v2 ? uda::colpack2_bound(104, n, buf_records) : uda::colpack_bound(104, n)));
+      const int64_t len = v2 ? uda::colpack2_encode(raw.data(), n, 104, buf_records, 3, 10, piece.data())
+                             : uda::colpack_encode(raw.data(), n, 104, buf_records, piece.data());
       uda::ColpackPiece p;
-      if (!uda::colpack_open(piece.data(), len, 104, n, &p) || !p.packed) return;
+      if (!uda::colpack_open(piece.data(), len, 104, n, &p) || !p.packed || p.delta != v2) return;
       res[(size_t)t].stride = p.stride;
       std::vector<uint8_t> stg((size_t)(buf_records * 104) * 2), kv((size_t)(buf_records * 104));
       auto pass = [&](int mode) {  // 0: unpack, 1: unpack + copy, 2: copy
@@ -115,9 +121,9 @@ int main(int argc, char** argv) {
     }
     u += r.unpack, uc += r.unpack_copy, c += r.copy;
   }
-  std::printf("{\"threads\": %d, \"mib_per_thread\": %lld, \"stride\": %lld, \"bmi2\": %s, \"path\": \"%s\", "
+  std::printf("{\"threads\": %d, \"mib_per_thread\": %lld, \"version\": %d, \"stride\": %lld, \"bmi2\": %s, \"path\": \"%s\", "
               "\"unpack_GBps_per_thread\": %.2f, \"unpack_copy_GBps_per_thread\": %.2f, \"copy_GBps_per_thread\": %.2f}\n",
-              threads, (long long)mib, (long long)res[0].stride, uda::colpack_have_bmi2() ? "true" : "false",
+              threads, (long long)mib, v2 ? 2 : 1, (long long)res[0].stride, uda::colpack_have_bmi2() ? "true" : "false",
               scalar || !uda::colpack_have_bmi2() ? "scalar" : "bmi2", u / threads / 1e9, uc / threads / 1e9,
               c / threads / 1e9);
   return 0;

@@ -768,10 +768,11 @@ ShuffleJob::ShuffleJob(const ShuffleConfig& cfg) : cfg_(cfg) {
   if (cfg_.d2h != "sdma" && cfg_.d2h != "hip") throw std::runtime_error("ShuffleJob: d2h must be sdma or hip");
   if (cfg_.store != "hbm" && cfg_.store != "host" && cfg_.store != "disk")
     throw std::runtime_error("unknown store tier " + cfg_.store);
-  if (cfg_.delivery_pack != "auto" && cfg_.delivery_pack != "off")
-    throw std::runtime_error("ShuffleJob: delivery_pack must be auto or off");
+  if (cfg_.delivery_pack != "auto" && cfg_.delivery_pack != "v1" && cfg_.delivery_pack != "off")
+    throw std::runtime_error("ShuffleJob: delivery_pack must be auto, v1 or off");
   check_delivery_order(cfg_.delivery_order);
-  pack_ = cfg_.deliver_host && cfg_.delivery_pack == "auto";
+  pack_ = cfg_.deliver_host && cfg_.delivery_pack != "off";
+  pack_version_ = cfg_.delivery_pack == "v1" ? (int)kColpackVersion : (int)kColpackVersion2;
   if (const char* e = std::getenv("UDA_DELIVERY_PACK"))
     if (std::atoi(e) == 0) pack_ = false;
   R_ = cfg_.reducers;
@@ -794,8 +795,7 @@ ShuffleJob::ShuffleJob(const ShuffleConfig& cfg) : cfg_(cfg) {
   const int64_t buf_bytes = buf_records_ * kTeraRecordBytes;
   piece_bytes_ = std::max<int64_t>(1, cfg_.d2h_piece_bytes / buf_bytes) * buf_bytes;
   // a packed piece of few records is longer than the records themselves (header, padding)
-  ring_stride_ = pack_ ? std::max(piece_bytes_, colpack_bound(kTeraRecordBytes, piece_bytes_ / kTeraRecordBytes))
-                       : piece_bytes_;
+  ring_stride_ = pack_ ? std::max(piece_bytes_, pack_bound(piece_bytes_ / kTeraRecordBytes)) : piece_bytes_;
   merged_ev_.resize(kSlots);
   comm_ev_.resize(kSlots);
   sent_ev_.resize(2);
@@ -860,7 +860,8 @@ std::string ShuffleJob::delivery_name() const {
   std::string name = sdma_ ? sdma_->describe() : "hip[numa=" + std::to_string(device_numa_node(cfg_.device)) + "]";
   name += " ring=" + ring_numa_ + " order=" + cfg_.delivery_order;
   if (!pack_) return name + " pack=off";
-  name += " pack=colbits";
+  name += " pack=colbits v" + std::to_string(pack_version_);
+  if (last_delta_ >= 0) name += last_delta_ ? " delta" : " plain";  // the last step's pieces
   if (last_d2h_ratio_ >= 0) {  // the last step's d2h_bytes / bytes_in
     char b[32];
     std::snprintf(b, sizeof(b), " d2h/in=%.3f", last_d2h_ratio_);
@@ -869,13 +870,18 @@ std::string ShuffleJob::delivery_name() const {
   return name;
 }
 
+int64_t ShuffleJob::pack_bound(int64_t nrec) const {
+  return pack_version_ == (int)kColpackVersion ? colpack_bound(kTeraRecordBytes, nrec)
+                                               : colpack2_bound(kTeraRecordBytes, nrec, buf_records_);
+}
+
 std::vector<ShuffleJob::PackPiece> ShuffleJob::round_pieces(const std::vector<int64_t>& group_recs) const {
   std::vector<PackPiece> v;
   int64_t doff = 0;
   for (const DeliveryPiece& dp : delivery_schedule(group_recs, piece_bytes_, "reducer", kTeraRecordBytes)) {
     const int64_t nrec = dp.len / kTeraRecordBytes;
     v.push_back(PackPiece{dp.src_off, doff, nrec});
-    doff += colpack_bound(kTeraRecordBytes, nrec);
+    doff += pack_bound(nrec);
   }
   return v;
 }
@@ -1355,7 +1361,7 @@ void ShuffleJob::compute_plans() {
       max_pieces = std::max(max_pieces, pack_n_[q]);
       for (const PackPiece& pc : pieces[q]) {
         pack_max_nrec_[q] = std::max(pack_max_nrec_[q], pc.nrec);
-        packed_bytes = std::max(packed_bytes, pc.dst_off + colpack_bound(kTeraRecordBytes, pc.nrec));
+        packed_bytes = std::max(packed_bytes, pc.dst_off + pack_bound(pc.nrec));
       }
     }
     packed_slots_.resize(kSlots);
@@ -1666,7 +1672,7 @@ void ShuffleJob::copy_loop() {
             throw std::runtime_error("delivery_pack: piece list out of step with the copy loop");
           const ColpackResult pr = pres[issued];
           if (pr.packed) {
-            if (pr.bytes < (int64_t)kColpackHeaderBytes || pr.bytes > colpack_bound(kTeraRecordBytes, ppieces[pi].nrec))
+            if (pr.bytes < (int64_t)kColpackHeaderBytes || pr.bytes > pack_bound(ppieces[pi].nrec))
               throw std::runtime_error("delivery_pack: packed length outside the piece's region");
             packed = true;
             copy_len = pr.bytes;
@@ -1689,6 +1695,12 @@ void ShuffleJob::copy_loop() {
           items_[dp.reducer].push_back(Item{k, dp.len, last_round && dp.last_of_reducer, now, r.q, packed, copy_len});
           step_d2h_bytes_ += copy_len;
           ++(packed ? step_packed_ : step_raw_);
+          if (packed) {
+            const ColpackResult pr = pres[issued - 1];
+            step_delta_ += pr.delta ? 1 : 0;
+            step_stride_min_ = step_stride_min_ < 0 ? (int64_t)pr.stride : std::min<int64_t>(step_stride_min_, pr.stride);
+            step_stride_max_ = std::max<int64_t>(step_stride_max_, pr.stride);
+          }
         }
         cv_.notify_all();
       }
@@ -1928,7 +1940,9 @@ StepStats ShuffleJob::run_step(bool validate) {
     step_buffers_ = 0;
     step_error_ = 0;
     step_d2h_ms_ = 0;
-    step_d2h_bytes_ = step_packed_ = step_raw_ = 0;
+    step_d2h_bytes_ = step_packed_ = step_raw_ = step_delta_ = 0;
+    step_stride_min_ = -1;
+    step_stride_max_ = 0;
     step_unpack_ms_ = 0;
     step_t0_ms_ = t0;
     first_issue_ms_ = last_landing_ms_ = idle_since_ms_ = eof_done_ms_ = -1;
@@ -2229,7 +2243,7 @@ StepStats ShuffleJob::run_step(bool validate) {
       auto pack_range = [&](int a, int b) {
         launch_colpack(d_pack_pieces_[q].as<ColpackPieceDesc>() + a, b - a, pack_max_nrec_[q], kTeraRecordBytes,
                        buf_records_, d_pack_table_.as<uint32_t>(), d_pack_results_[slot].as<ColpackResult>() + a,
-                       s_compute_);
+                       s_compute_, pack_version_, kTeraKeyOffset, kTeraKeyBytes);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(h_pack_results_[slot].as<ColpackResult>() + a,
                                  d_pack_results_[slot].as<ColpackResult>() + a, (size_t)(b - a) * sizeof(ColpackResult),
@@ -2294,6 +2308,10 @@ StepStats ShuffleJob::run_step(bool validate) {
     st.d2h_bytes = step_d2h_bytes_;
     st.packed_pieces = step_packed_;
     st.raw_pieces = step_raw_;
+    st.pack_delta_pieces = step_delta_;
+    st.pack_stride_min = std::max<int64_t>(step_stride_min_, 0);
+    st.pack_stride_max = step_stride_max_;
+    if (deliver && pack_) last_delta_ = step_packed_ > 0 && step_delta_ == step_packed_ ? 1 : 0;
     st.unpack_ms = step_unpack_ms_;
     st.slot_wait_ms = step_slot_wait_ms_;
     if (first_issue_ms_ >= 0) {  // every piece has landed and every EOF is out by now

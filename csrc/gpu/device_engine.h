@@ -279,7 +279,8 @@ struct ShuffleConfig {
   bool check_delivery = false;
   // "auto" (on): merged records are bit-packed per column on the device before their D2H (colpack,
   // codec/colpack.h) and unpacked by the consumer threads right before the sink; "off": sent as they
-  // are. UDA_DELIVERY_PACK=0 forces off.
+  // are. "auto" packs with colpack version 2 (key differences, bit-contiguous rows), "v1" with version 1.
+  // UDA_DELIVERY_PACK=0 forces off.
   std::string delivery_pack = "auto";
   // order the copy thread issues a round's D2H pieces in (delivery_schedule.h): "wave" (piece 0 of every
   // reducer, then piece 1 of every reducer, ...: every consumer drains at once) or "reducer" (all pieces
@@ -303,6 +304,9 @@ struct StepStats {
   int64_t d2h_bytes = 0;       // bytes the delivery copied over the link (packed pieces: their packed length)
   int64_t packed_pieces = 0;   // delivery pieces sent bit-packed (colpack)
   int64_t raw_pieces = 0;      // delivery pieces sent as they are
+  int64_t pack_delta_pieces = 0;  // packed pieces whose key columns hold key differences (colpack version 2)
+  int64_t pack_stride_min = 0;    // smallest and largest packed row stride among the step's packed pieces
+  int64_t pack_stride_max = 0;
   double unpack_ms = 0;        // host time the consumer threads spent unpacking (summed over consumers)
   // link occupancy of the delivery, from the copy thread's issues and the landings seen by whoever waits on
   // a piece's signal or event; lead_in_ms + link_idle_ms + tail_ms <= wall_ms
@@ -496,7 +500,9 @@ class ShuffleJob {
   // the D2H pieces of a round, reducer-major: delivery_schedule()'s pack_index numbers them (reducers with
   // no records this round have none)
   std::vector<PackPiece> round_pieces(const std::vector<int64_t>& group_recs) const;
+  int64_t pack_bound(int64_t nrec) const;      // a piece's region in the packed slot and the ring
   bool pack_ = false;
+  int pack_version_ = 2;                       // colpack format version of the packed pieces
   std::vector<DeviceBuffer> packed_slots_;     // per slot
   std::vector<DeviceBuffer> d_pack_pieces_;    // per round: ColpackPieceDesc[pack_n_[q]], in issue order
   std::vector<int> pack_n_;
@@ -512,6 +518,7 @@ class ShuffleJob {
   std::vector<PinnedBuffer> h_pack_results_;
   int64_t ring_stride_ = 0;                    // bytes per pinned ring slot (>= piece_bytes_)
   double last_d2h_ratio_ = -1;                 // last step: d2h_bytes / bytes_in
+  int last_delta_ = -1;                        // last step: 1 when every packed piece was delta, -1: no step yet
 
   // ---- delivery: copy thread -> pinned ring (SDMA) -> per-reducer consumer threads
   std::unique_ptr<SdmaEngine> sdma_;
@@ -548,7 +555,8 @@ class ShuffleJob {
   int step_error_ = 0;
   std::string step_error_msg_;
   double step_d2h_ms_ = 0;
-  int64_t step_d2h_bytes_ = 0, step_packed_ = 0, step_raw_ = 0;
+  int64_t step_d2h_bytes_ = 0, step_packed_ = 0, step_raw_ = 0, step_delta_ = 0;
+  int64_t step_stride_min_ = -1, step_stride_max_ = 0;
   double step_unpack_ms_ = 0;
   // link occupancy (StepStats lead_in_ms ...), all under mu_. A piece is in flight from its issue until
   // someone sees its signal or event complete; slot_flying_[k]: ring slot k holds such a piece.

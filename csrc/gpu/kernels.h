@@ -237,21 +237,26 @@ void launch_batched_copy(const CopyDesc* descs, int n, int64_t max_bytes, hipStr
 // Column-range bit-packing of fixed-length record pieces ahead of their D2H (codec/colpack.h).
 struct ColpackPieceDesc {
   const uint8_t* src;  // nrec records of L bytes
-  uint8_t* dst;        // the piece's region in the packed slot: colpack_bound(L, nrec) bytes, 64-byte aligned
+  uint8_t* dst;        // the piece's region in the packed slot, 64-byte aligned: colpack_bound(L, nrec) bytes
+                       // (version 2: colpack2_bound(L, nrec, buf_records))
   int64_t nrec;        // >= 1
 };
 struct ColpackResult {
   int64_t bytes;    // length of the piece at dst (header only when raw)
   uint32_t packed;  // 0: raw, the records are to be sent as they are
   uint32_t stride;
+  uint32_t delta;   // version 2: the key columns hold key differences
+  uint32_t reserved;
 };
 // Device bytes of the per-piece min/max table launch_colpack works in.
 size_t colpack_table_bytes(int npieces);
 // colpack_stats_kernel, colpack_plan_kernel, colpack_pack_kernel over the device array of npieces
 // (<= 65535) descriptors; L <= kColpackMaxRecordBytes. max_nrec: largest piece (sizes the grids).
-// results[p] and the bytes at pieces[p].dst equal the host reference encoder's (colpack_encode).
+// results[p] and the bytes at pieces[p].dst equal the host reference encoder's: colpack_encode for
+// version 1 (the key field is ignored), colpack2_encode(.., key_off, key_len, ..) for version 2.
 void launch_colpack(const ColpackPieceDesc* pieces, int npieces, int64_t max_nrec, int L, int64_t buf_records,
-                    uint32_t* table, ColpackResult* results, hipStream_t s);
+                    uint32_t* table, ColpackResult* results, hipStream_t s, int version = 1, int key_off = 0,
+                    int key_len = 0);
 
 // ---------------------------------------------------------------- block decode (F6)
 // One Hadoop compressed block: chunks [u32 BE clen][clen bytes]... in [src, src_end) of the

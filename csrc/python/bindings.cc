@@ -76,6 +76,9 @@ py::dict stats_to_dict(const gpu::StepStats& s) {
   d["buffers"] = s.buffers;
   d["d2h_bytes"] = s.d2h_bytes;
   d["packed_pieces"] = s.packed_pieces;
+  d["pack_delta_pieces"] = s.pack_delta_pieces;
+  d["pack_stride_min"] = s.pack_stride_min;
+  d["pack_stride_max"] = s.pack_stride_max;
   d["raw_pieces"] = s.raw_pieces;
   d["unpack_ms"] = s.unpack_ms;
   d["lead_in_ms"] = s.lead_in_ms;
@@ -374,6 +377,19 @@ PYBIND11_MODULE(_uda_native, m) {
     out.resize((size_t)n);
     return py::bytes(out);
   }, py::arg("records"), py::arg("record_bytes"), py::arg("buf_records") = 1);
+  // version 2 of the format: key differences (key field key_off, key_len; 0: no key) and bit-contiguous rows
+  m.def("colpack2_encode", [](py::bytes b, int L, int64_t buf_records, int key_off, int key_len) {
+    std::string s = b;
+    if (L < 1 || L > kColpackMaxRecordBytes || s.empty() || s.size() % (size_t)L)
+      throw py::value_error("colpack2_encode: need whole records of 1..256 bytes");
+    if (key_off < 0 || key_len < 0 || key_len > kColpackMaxKeyBytes || key_off + key_len > L)
+      throw py::value_error("colpack2_encode: key field outside the record or longer than 16 bytes");
+    const int64_t nrec = (int64_t)s.size() / L;
+    std::string out((size_t)colpack2_bound(L, nrec, buf_records), '\0');
+    const int64_t n = colpack2_encode((const uint8_t*)s.data(), nrec, L, buf_records, key_off, key_len, (uint8_t*)&out[0]);
+    out.resize((size_t)n);
+    return py::bytes(out);
+  }, py::arg("records"), py::arg("record_bytes"), py::arg("buf_records"), py::arg("key_off"), py::arg("key_len"));
   // path: "auto", "bmi2" or "scalar"; rows [row0, row0 + rows) (rows < 0: to the end). Raises ValueError for a
   // piece whose header fails its checks, or that is marked raw.
   m.def("colpack_decode", [](py::bytes b, int expect_L, int64_t expect_records, const std::string& path, int64_t row0,
@@ -399,8 +415,12 @@ PYBIND11_MODULE(_uda_native, m) {
      py::arg("row0") = 0, py::arg("rows") = -1);
   // The three device kernels over `pieces` (each a bytes object of whole records of record_bytes): returns
   // per piece (the bytes the kernels wrote: header, rows, padding; packed flag; stride).
-  m.def("gpu_colpack_encode", [](const std::vector<std::string>& pieces, int L, int64_t buf_records, int device) {
+  auto gpu_encode = [](const std::vector<std::string>& pieces, int L, int64_t buf_records, int device, int version,
+                       int key_off, int key_len) {
     if (L < 1 || L > kColpackMaxRecordBytes || pieces.empty()) throw py::value_error("gpu_colpack_encode: bad arguments");
+    if (key_off < 0 || key_len < 0 || key_len > kColpackMaxKeyBytes || key_off + key_len > L)
+      throw py::value_error("gpu_colpack_encode: key field outside the record or longer than 16 bytes");
+    auto bound = [&](int64_t n) { return version == 2 ? colpack2_bound(L, n, buf_records) : colpack_bound(L, n); };
     std::vector<int64_t> src_off, dst_off, nrec;
     int64_t src_bytes = 0, dst_bytes = 0, max_nrec = 0;
     for (const auto& s : pieces) {
@@ -410,7 +430,7 @@ PYBIND11_MODULE(_uda_native, m) {
       nrec.push_back((int64_t)s.size() / L);
       max_nrec = std::max(max_nrec, nrec.back());
       src_bytes += ((int64_t)s.size() + 7) / 8 * 8;
-      dst_bytes += colpack_bound(L, nrec.back());
+      dst_bytes += bound(nrec.back());
     }
     const int n = (int)pieces.size();
     std::vector<gpu::ColpackResult> res((size_t)n);
@@ -434,13 +454,13 @@ PYBIND11_MODULE(_uda_native, m) {
       hipStream_t s = nullptr;
       HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
       gpu::launch_colpack(ddesc.as<gpu::ColpackPieceDesc>(), n, max_nrec, L, buf_records, dtab.as<uint32_t>(),
-                          dres.as<gpu::ColpackResult>(), s);
+                          dres.as<gpu::ColpackResult>(), s, version, key_off, key_len);
       HIP_CHECK(hipGetLastError());
       HIP_CHECK(hipStreamSynchronize(s));
       HIP_CHECK(hipStreamDestroy(s));
       HIP_CHECK(hipMemcpy(res.data(), dres.as(), res.size() * sizeof(res[0]), hipMemcpyDeviceToHost));
       for (int i = 0; i < n; ++i) {
-        if (res[(size_t)i].bytes < 0 || res[(size_t)i].bytes > colpack_bound(L, nrec[i]))
+        if (res[(size_t)i].bytes < 0 || res[(size_t)i].bytes > bound(nrec[i]))
           throw std::runtime_error("gpu_colpack_encode: a piece's length is outside its region");
         out[(size_t)i].resize((size_t)res[(size_t)i].bytes);
         HIP_CHECK(hipMemcpy(&out[(size_t)i][0], ddst.as<uint8_t>() + dst_off[i], out[(size_t)i].size(), hipMemcpyDeviceToHost));
@@ -450,7 +470,15 @@ PYBIND11_MODULE(_uda_native, m) {
     for (int i = 0; i < n; ++i)
       ret.append(py::make_tuple(py::bytes(out[(size_t)i]), res[(size_t)i].packed != 0, (int64_t)res[(size_t)i].stride));
     return ret;
+  };
+  m.def("gpu_colpack_encode", [gpu_encode](const std::vector<std::string>& pieces, int L, int64_t buf_records, int device) {
+    return gpu_encode(pieces, L, buf_records, device, 1, 0, 0);
   }, py::arg("pieces"), py::arg("record_bytes"), py::arg("buf_records") = 1, py::arg("device") = 0);
+  m.def("gpu_colpack2_encode", [gpu_encode](const std::vector<std::string>& pieces, int L, int64_t buf_records,
+                                            int key_off, int key_len, int device) {
+    return gpu_encode(pieces, L, buf_records, device, 2, key_off, key_len);
+  }, py::arg("pieces"), py::arg("record_bytes"), py::arg("buf_records"), py::arg("key_off"), py::arg("key_len"),
+     py::arg("device") = 0);
   m.def("codec_from_class", [](const std::string& c) {
     bool unsup = false;
     int v = (int)codec_from_class(c, &unsup);

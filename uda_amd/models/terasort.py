@@ -55,7 +55,8 @@ class TeraSortConfig:
     replan: bool = False                # every step recomputes the cell splits and exchanges the counts
     map_sort: bool = False              # setup: unsorted map input sorted on the device (F8 radix sort)
     check_delivery: bool = False        # validate steps: checksum every round output before its D2H and as received
-    delivery_pack: str = "auto"         # "auto": bit-pack merged records per column before their D2H; "off"
+    delivery_pack: str = "auto"         # "auto": bit-pack merged records per column before their D2H (colpack
+                                        # version 2: key differences, bit-contiguous rows); "v1": version 1; "off"
     delivery_order: str = "wave"        # a round's D2H pieces: "wave" (piece k of every reducer in turn) or "reducer"
     exchange: str = "ipc"               # world > 1: "ipc" (shared-memory control + hipIpc pulls) or "rccl"
 
