@@ -44,6 +44,7 @@
 #include "../gpu/device_ptr.h"
 #include "../gpu/device_reduce.h"
 #include "../gpu/device_engine.h"
+#include "../gpu/fixed_delivery.h"
 #include "../gpu/generic_merger.h"
 #include "../gpu/generic_rounds.h"
 #include "../gpu/hbm_ledger.h"
@@ -1003,6 +1004,8 @@ void prewarm_node_merges(int device, int tasks, int64_t round_bytes, int maps, i
   cfg.device = device;
   cfg.kv_buf_bytes = kv_buf;
   cfg.round_bytes = round_bytes;
+  // the hosted tasks' defaults (mapred.uda.gpu.delivery.pack): their ring blocks carry the unpack staging
+  cfg.pack_version = std::max(0, gpu::delivery_pack_version("auto"));
   gpu::prewarm_device_reduce(cfg, std::max(1, maps), tasks);
 }
 
@@ -1051,6 +1054,8 @@ void ReduceTask::prewarm_gpu(PrewarmConf pc) {
       cfg.device = device;
       cfg.kv_buf_bytes = kv_buf_size_;
       cfg.round_bytes = pc.round_bytes;
+      cfg.pack_version = pc.delivery_pack;
+      cfg.piece_bytes = pc.delivery_piece_bytes;
       gpu::prewarm_device_reduce(cfg, std::max(1, pc.maps));
     }
     lap("fixed10");
@@ -2813,6 +2818,8 @@ bool ReduceTask::merge_gpu_device(bool probe) {
       cfg.device = device;
       cfg.kv_buf_bytes = kv_buf_size_;
       cfg.round_bytes = round_bytes;
+      cfg.pack_version = delivery_pack_;
+      cfg.piece_bytes = delivery_piece_bytes_;
       cfg.stop = [&] { return stop_.load(); };
       // the node's tasks take turns for each round's block decode (FIFO, this many at once; 0 = no
       // limit). One round's decode (a wave per 256 KiB block, ~8k blocks) leaves the device idle: 130 GB
@@ -2838,6 +2845,10 @@ bool ReduceTask::merge_gpu_device(bool probe) {
         st_.gpu_device_ms = ds.plan_ms + ds.merge_wait_ms;
         st_.gpu_d2h_wait_ms = ds.d2h_wait_ms;
         st_.gpu_sink_ms = ds.sink_ms;
+        st_.gpu_d2h_bytes = ds.d2h_bytes;
+        st_.gpu_packed_pieces = ds.packed_pieces;
+        st_.gpu_raw_pieces = ds.raw_pieces;
+        st_.gpu_unpack_ms = ds.unpack_ms;
         st_.fetch_ms = fetch_ms;
         st_.merge_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - fetch_ms;
         st_.merge_path = "device-fixed10-stream";
@@ -2849,8 +2860,12 @@ bool ReduceTask::merge_gpu_device(bool probe) {
       // decode output and the merge's rounds at once: a task holding its decoded partitions must
       // not then wait for merge memory behind tasks doing the same
       const int64_t raw = bp.raw_total;
+      gpu::DeviceReduceConfig pcfg;  // the merge below packs its delivery: the packed slots count too
+      pcfg.kv_buf_bytes = kv_buf_size_;
+      pcfg.pack_version = delivery_pack_;
+      pcfg.piece_bytes = delivery_piece_bytes_;
       admit(std::max<int64_t>(0, raw + raw / 8 - (int64_t)ws.in.held()), [&](int64_t rb) {
-        return gpu::fixed_round_ws_bytes(std::min(rb, raw), (int)parts.size());
+        return gpu::fixed_round_ws_bytes(std::min(rb, raw), (int)parts.size(), &pcfg);
       });
     }
     // Decodes of concurrent tasks take turns (FIFO, mapred.uda.gpu.decode.slots at once, default 1;
@@ -2916,6 +2931,8 @@ bool ReduceTask::merge_gpu_device(bool probe) {
     cfg.device = device;
     cfg.kv_buf_bytes = kv_buf_size_;
     cfg.round_bytes = round_bytes;
+    cfg.pack_version = delivery_pack_;
+    cfg.piece_bytes = delivery_piece_bytes_;
     cfg.stop = [&] { return stop_.load(); };
     gpu::DeviceReduceStats ds = gpu::device_reduce_fixed(cfg, runs, sink);
     std::lock_guard<std::mutex> g(st_mu_);
@@ -2929,6 +2946,10 @@ bool ReduceTask::merge_gpu_device(bool probe) {
     st_.gpu_device_ms = ds.plan_ms + ds.merge_wait_ms;
     st_.gpu_d2h_wait_ms = ds.d2h_wait_ms;
     st_.gpu_sink_ms = ds.sink_ms;
+    st_.gpu_d2h_bytes = ds.d2h_bytes;
+    st_.gpu_packed_pieces = ds.packed_pieces;
+    st_.gpu_raw_pieces = ds.raw_pieces;
+    st_.gpu_unpack_ms = ds.unpack_ms;
     st_.fetch_ms = fetch_ms;
     st_.merge_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - fetch_ms;
     st_.merge_path = "device-fixed10";

@@ -18,6 +18,7 @@
 #include <random>
 #include <sstream>
 
+#include "../gpu/fixed_delivery.h"
 #include "../gpu/hbm_ledger.h"
 #include "uda/log.h"
 #include "uda/node_registry.h"
@@ -447,6 +448,15 @@ void ReduceTask::on_init(const InitParams& p_in) {
     UDA_LOG(kInfo, "mapred.uda.merge.backend=auto: %s merge", backend_.c_str());
   }
   if (backend_ != "cpu" && backend_ != "gpu") throw ProtocolError("unknown mapred.uda.merge.backend " + backend_);
+  if (backend_ == "gpu") {
+    // FIXED10 delivery: bit-packed D2H pieces (gpu/fixed_delivery.h) and the D2H granule
+    const std::string pack = host_->get_conf("mapred.uda.gpu.delivery.pack", "auto");
+    delivery_pack_ = gpu::delivery_pack_version(pack);
+    if (delivery_pack_ < 0) throw ProtocolError("unknown mapred.uda.gpu.delivery.pack \"" + pack + "\" (auto, v1 or off)");
+    delivery_piece_bytes_ = host_->conf_i64("mapred.uda.gpu.delivery.piece.bytes", 64ll << 20);
+    if (delivery_piece_bytes_ < 1)
+      throw ProtocolError("mapred.uda.gpu.delivery.piece.bytes must be positive, got " + std::to_string(delivery_piece_bytes_));
+  }
   // the reference's consumer always fetches over the network from the providers (RdmaClient,
   // src/Merger/reducer.cc:412-437); loopback only reaches a provider in this very process
   const std::string tr = host_->get_conf("mapred.uda.transport", "tcp");
@@ -479,6 +489,8 @@ void ReduceTask::on_init(const InitParams& p_in) {
       pc.pinned_bytes = host_->conf_i64("mapred.uda.gpu.prewarm.pinned.mb", 1024) << 20;
     pc.round_bytes = host_->conf_i64("mapred.uda.gpu.round.bytes", 2ll << 30);
     pc.maps = p.num_maps;
+    pc.delivery_pack = delivery_pack_;
+    pc.delivery_piece_bytes = delivery_piece_bytes_;
     prewarm_thr_ = std::thread([this, pc] { name_thread("uda-task-warm"); prewarm_gpu(pc); });
   }
   merge_thr_ = std::thread([this] { name_thread("uda-task-merge"); merge_main(); });
@@ -930,7 +942,8 @@ std::string ReduceTask::stats_json() const {
     << ",\"total_ms\":" << s.total_ms << ",\"device_decoded_blocks\":" << s.device_decoded_blocks
     << ",\"rpq_rounds\":" << s.rpq_rounds << ",\"hybrid_direct\":" << s.hybrid_direct << ",\"merge_budget_from_ledger\":" << s.merge_budget_from_ledger << ",\"gpu_h2d_ms\":" << s.gpu_h2d_ms
     << ",\"gpu_device_ms\":" << s.gpu_device_ms << ",\"gpu_d2h_wait_ms\":" << s.gpu_d2h_wait_ms
-    << ",\"gpu_sink_ms\":" << s.gpu_sink_ms << ",\"gpu_decode_ms\":" << s.gpu_decode_ms << ",\"gpu_gate_wait_ms\":" << s.gpu_gate_wait_ms << ",\"gpu_prewarm_ms\":" << s.gpu_prewarm_ms << ",\"gpu_prewarm_wait_ms\":" << s.gpu_prewarm_wait_ms << ",\"gpu_prewarm_phases\":\"" << json_escape(s.gpu_prewarm_phases) << "\"" << ",\"fetch_buf_bytes\":" << s.fetch_buf_bytes
+    << ",\"gpu_sink_ms\":" << s.gpu_sink_ms << ",\"gpu_d2h_bytes\":" << s.gpu_d2h_bytes << ",\"gpu_packed_pieces\":" << s.gpu_packed_pieces
+    << ",\"gpu_raw_pieces\":" << s.gpu_raw_pieces << ",\"gpu_unpack_ms\":" << s.gpu_unpack_ms << ",\"gpu_decode_ms\":" << s.gpu_decode_ms << ",\"gpu_gate_wait_ms\":" << s.gpu_gate_wait_ms << ",\"gpu_prewarm_ms\":" << s.gpu_prewarm_ms << ",\"gpu_prewarm_wait_ms\":" << s.gpu_prewarm_wait_ms << ",\"gpu_prewarm_phases\":\"" << json_escape(s.gpu_prewarm_phases) << "\"" << ",\"fetch_buf_bytes\":" << s.fetch_buf_bytes
     << ",\"uncomp_buf_bytes\":" << s.uncomp_buf_bytes << ",\"restored_lpqs\":" << s.restored_lpqs
     << ",\"restored_maps\":" << s.restored_maps << ",\"device_descriptors\":" << s.device_descriptors << ",\"unmapped_descriptors\":" << s.unmapped_descriptors << ",\"unmapped_reason\":\"" << json_escape(s.unmapped_reason) << "\"" << ",\"descriptor_map_ms\":" << s.descriptor_map_ms << ",\"fetch_cmd_wait_ms\":" << s.fetch_cmd_wait_ms << ",\"fetch_ack_wait_ms\":" << s.fetch_ack_wait_ms << ",\"merge_start_boot_ms\":" << std::fixed << std::setprecision(1) << s.merge_start_boot_ms << ",\"fetch_sent_boot_ms\":" << s.fetch_sent_boot_ms << std::defaultfloat << std::setprecision(6) << ",\"first_data_ms\":" << s.first_data_ms << ",\"gpu_ws_bytes\":" << s.gpu_ws_bytes
     << ",\"host_fetched_bytes\":" << s.host_fetched_bytes << ",\"local_read_bytes\":" << s.local_read_bytes << ",\"hbm_wait_ms\":" << s.hbm_wait_ms

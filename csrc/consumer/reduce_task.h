@@ -62,6 +62,10 @@ struct ReduceStats {
   // GPU backend phase split: H2D staging, device decode+merge, waits on D2H pieces, host consumers
   // (dataFromUda / spill writes) of the pinned pieces
   double gpu_h2d_ms = 0, gpu_device_ms = 0, gpu_d2h_wait_ms = 0, gpu_sink_ms = 0;
+  // FIXED10 device paths: bytes that crossed the link for the merged records, D2H pieces sent bit-packed /
+  // as records (mapred.uda.gpu.delivery.pack), host unpack time
+  int64_t gpu_d2h_bytes = 0, gpu_packed_pieces = 0, gpu_raw_pieces = 0;
+  double gpu_unpack_ms = 0;
   double gpu_decode_ms = 0;  // device fetch, compressed partitions: framing walk + F6 decode (stream synced)
   double gpu_gate_wait_ms = 0;  // waiting for a GPU merge slot (mapred.uda.gpu.max.concurrent.merges)
   double hbm_wait_ms = 0;       // waiting for the device working set under the HBM budget
@@ -169,6 +173,8 @@ class ReduceTask {
     int64_t pinned_bytes = 0;
     int64_t round_bytes = 2ll << 30;
     int maps = 0;
+    int delivery_pack = 2;
+    int64_t delivery_piece_bytes = 64ll << 20;
   };
   void prewarm_gpu(PrewarmConf pc);
   void join_prewarm();
@@ -184,6 +190,8 @@ class ReduceTask {
   std::string device_conf_ = "auto";   // read on the INIT thread
   std::string fault_spec_;             // mapred.uda.fault.inject (tests: faults of this task only)
   double hbm_budget_conf_ = 0;
+  int delivery_pack_ = 2;                       // mapred.uda.gpu.delivery.pack: colpack version, 0 = off
+  int64_t delivery_piece_bytes_ = 64ll << 20;   // mapred.uda.gpu.delivery.piece.bytes
   int device_ = 0;
   int registry_slot_ = -1;
   // Fetch `n` MOFs into `q` (reference merge_do_fetching_phase).

@@ -18,7 +18,9 @@
 #include <thread>
 
 #include "block_decoder.h"
+#include "codec/colpack.h"
 #include "device_engine.h"
+#include "fixed_delivery.h"
 #include "hbm_ledger.h"
 #include "sdma.h"
 #include "uda/error.h"
@@ -63,6 +65,13 @@ struct FixedWs {
   // streaming decode of block-compressed runs (device_reduce_fixed_blocks): the round inputs, the block
   // prefixes + first keys, and the per-round decode descriptors
   DeviceBuffer in[2], prefix, d_first, d_keys, d_descs[2];
+  // packed delivery (DeviceReduceConfig::pack_version): the device ring of packed pieces, the piece
+  // descriptors and results of its two groups, the kernels' min/max table, the pinned host copies of
+  // descriptors and results, the pack stream and one event per group
+  DeviceBuffer pring, d_pk_desc, d_pk_res, d_pk_table;
+  std::unique_ptr<PinnedBuffer> h_pk;
+  hipStream_t ps = nullptr;
+  hipEvent_t packed_ev[2] = {nullptr, nullptr};
   hipStream_t s = nullptr;
   hipStream_t ds = nullptr;  // streaming decode: round decodes and cuts, beside the merges on s
   hipEvent_t merged[2] = {nullptr, nullptr};
@@ -76,6 +85,12 @@ struct FixedWs {
       (void)hipStreamSynchronize(ds);
       (void)hipStreamDestroy(ds);
     }
+    if (ps) {
+      (void)hipStreamSynchronize(ps);
+      (void)hipStreamDestroy(ps);
+    }
+    for (auto e : packed_ev)
+      if (e) (void)hipEventDestroy(e);
     for (auto e : merged)
       if (e) (void)hipEventDestroy(e);
     if (s) (void)hipStreamDestroy(s);
@@ -88,7 +103,8 @@ struct FixedWs {
   int64_t device_bytes() const {
     int64_t n = merger ? merger->device_bytes() : 0;
     for (const DeviceBuffer* b : {&out[0], &out[1], &d_bases, &d_nrec, &d_soff, &d_samp, &d_bset, &d_out, &d_bounds,
-                                  &d_runs, &flag, &in[0], &in[1], &prefix, &d_first, &d_keys, &d_descs[0], &d_descs[1]})
+                                  &d_runs, &flag, &in[0], &in[1], &prefix, &d_first, &d_keys, &d_descs[0], &d_descs[1],
+                                  &pring, &d_pk_desc, &d_pk_res, &d_pk_table})
       n += (int64_t)b->held();
     return n;
   }
@@ -201,22 +217,212 @@ struct Ring {
     eng.release_ring(p, bytes);
   }
 };
+
+// ---- packed delivery: a device ring of 2 * slots piece regions (two groups of `slots` pieces: one is
+// copied to the host while the next is packed), far smaller than round-sized packed slots: 16 tasks of
+// 2 GiB rounds next to a 130 GB store stay inside the HBM budget without waiting for one another.
+struct PackNeed {
+  int64_t np = 0, ring = 0, desc = 0, res = 0, table = 0;
+};
+PackNeed pack_need(const FixedLayout& l, int64_t max_recs) {
+  PackNeed n;
+  if (l.pack_version == 0 || max_recs <= 0) return n;
+  n.np = std::min<int64_t>(2 * l.slots, (max_recs + l.piece_recs - 1) / l.piece_recs);
+  n.ring = n.np * l.region_bytes;
+  n.desc = n.np * (int64_t)sizeof(ColpackPieceDesc);
+  n.res = n.np * (int64_t)sizeof(ColpackResult);
+  n.table = (int64_t)colpack_table_bytes(l.slots);
+  return n;
+}
+// what pack_ensure(ws, l, max_recs) allocates (0 with pack off)
+int64_t pack_grow(const FixedWs& ws, const FixedLayout& l, int64_t max_recs) {
+  const PackNeed n = pack_need(l, max_recs);
+  if (n.np == 0) return 0;
+  return FixedWs::grow(ws.d_pk_table, n.table) + FixedWs::grow(ws.pring, n.ring) + FixedWs::grow(ws.d_pk_desc, n.desc) +
+         FixedWs::grow(ws.d_pk_res, n.res);
+}
+void pack_ensure(FixedWs& ws, const FixedLayout& l, int64_t max_recs) {
+  const PackNeed n = pack_need(l, max_recs);
+  if (n.np == 0) return;
+  FixedWs::ensure(ws.d_pk_table, (size_t)n.table);
+  FixedWs::ensure(ws.pring, (size_t)n.ring);
+  FixedWs::ensure(ws.d_pk_desc, (size_t)n.desc);
+  FixedWs::ensure(ws.d_pk_res, (size_t)n.res);
+  // descriptors and results in pinned host memory: a pageable async copy would stall the stream
+  const size_t host = (size_t)(2 * l.slots) * (sizeof(ColpackPieceDesc) + sizeof(ColpackResult));
+  if (!ws.h_pk || ws.h_pk->size() < host) {
+    ws.h_pk.reset();
+    ws.h_pk = std::make_unique<PinnedBuffer>();
+    ws.h_pk->alloc(host);
+  }
+  if (!ws.ps) {  // packs run beside the next round's merge (on s), ahead of it where the device has to choose
+    int lo = 0, hi = 0;
+    HIP_CHECK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+    HIP_CHECK(hipStreamCreateWithPriority(&ws.ps, hipStreamNonBlocking, hi));
+    for (auto& e : ws.packed_ev) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+}
+
+// The per-round delivery of both FIXED10 entry points. Round q's merged records lie in ws.out[q % 2];
+// deliver_round runs once the round's event has fired. Piece k is records [k * piece_recs, ...) of the
+// round; up to `slots` SDMA pieces are in flight into the pinned ring and each landed piece is handed on
+// by deliver_fixed_piece. Packed: pieces are bit-packed in groups of `slots` (launch_colpack on the
+// pack stream, results to pinned host memory) into the two halves of the device ring; group j + 2 is
+// packed once every piece of group j has landed on the host, so a group is packed while the one before
+// it crosses the link.
+class FixedDelivery {
+ public:
+  FixedDelivery(const DeviceReduceConfig& cfg, const FixedLayout& lay, FixedWs& ws, DeviceReduceStats& st,
+                const FixedSink& sink)
+      : lay_(lay), ws_(ws), st_(st), sink_(sink), ring_(SdmaEngine::for_device(cfg.device), lay.ring_bytes, lay.slots),
+        tail_((size_t)std::max(lay.kv_buf_bytes, lay.buf_bytes) + 16), held_((size_t)lay.slots) {
+    bufs_.tail = tail_.data();
+    if (lay_.pack_version != 0)
+      for (int i = 0; i < 2; ++i) bufs_.staging[i] = lay_.staging(ring_.p, i);
+  }
+
+  void deliver_round(int q, int64_t recs, bool last_round) {
+    const int par = q & 1;
+    const int S = lay_.slots;
+    const int64_t bytes = recs * kTeraRecordBytes, piece = lay_.piece;
+    const int64_t np = (bytes + piece - 1) / piece;
+    const uint8_t* src = ws_.out[par].as<uint8_t>();
+    const bool pack = lay_.pack_version != 0 && np > 0;
+    const int64_t groups = (np + S - 1) / S;
+    // pieces [j * S, ...) of the round into half j & 1 of the device ring
+    auto pack_group = [&](int64_t j) {
+      const int half = (int)(j & 1);
+      const int n = (int)std::min<int64_t>(S, np - j * S);
+      if ((int64_t)(half * S + n) * lay_.region_bytes > (int64_t)ws_.pring.size())
+        throw std::runtime_error("device reduce: a round with more pieces than its packed ring holds");
+      ColpackPieceDesc* hd = ws_.h_pk->as<ColpackPieceDesc>() + half * S;
+      for (int i = 0; i < n; ++i) {
+        const int64_t k = j * S + i;
+        hd[i] = ColpackPieceDesc{src + k * piece, ws_.pring.as<uint8_t>() + (int64_t)(half * S + i) * lay_.region_bytes,
+                                 std::min(lay_.piece_recs, recs - k * lay_.piece_recs)};
+      }
+      ColpackPieceDesc* dd = ws_.d_pk_desc.as<ColpackPieceDesc>() + half * S;
+      ColpackResult* dr = ws_.d_pk_res.as<ColpackResult>() + half * S;
+      HIP_CHECK(hipMemcpyAsync(dd, hd, (size_t)n * sizeof(ColpackPieceDesc), hipMemcpyHostToDevice, ws_.ps));
+      launch_colpack(dd, n, hd[0].nrec, (int)kTeraRecordBytes, lay_.buf_records, ws_.d_pk_table.as<uint32_t>(), dr, ws_.ps,
+                     lay_.pack_version, kTeraKeyOffset, kTeraKeyBytes);  // a group's first piece is its largest
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipMemcpyAsync(host_results() + half * S, dr, (size_t)n * sizeof(ColpackResult), hipMemcpyDeviceToHost, ws_.ps));
+      HIP_CHECK(hipEventRecord(ws_.packed_ev[half], ws_.ps));
+    };
+    int64_t ready = -1;  // last group whose results are on the host
+    SdmaEngine& eng = ring_.eng;
+    auto issue = [&](int64_t k) {
+      const int64_t off = k * piece, len = std::min(piece, bytes - off);
+      Held& h = held_[(size_t)(k % S)];
+      h = Held{len, false};
+      const uint8_t* from = src + off;
+      if (pack) {
+        const int64_t j = k / S;
+        const int at = (int)(j & 1) * S + (int)(k % S);
+        if (j > ready) {
+          const double a = now_ms();
+          HIP_CHECK(hipEventSynchronize(ws_.packed_ev[j & 1]));
+          st_.pack_wait_ms += now_ms() - a;
+          ready = j;
+        }
+        const ColpackResult pr = host_results()[at];
+        if (pr.packed) {
+          if (pr.bytes < (int64_t)kColpackHeaderBytes || pr.bytes > lay_.piece_bound(len / kTeraRecordBytes) ||
+              pr.bytes > lay_.slot_bytes)
+            throw std::runtime_error("device reduce: packed length outside the piece's region");
+          h = Held{pr.bytes, true};
+          from = ws_.pring.as<uint8_t>() + (int64_t)at * lay_.region_bytes;
+          st_.delta_pieces += pr.delta ? 1 : 0;
+        }
+      }
+      hsa_signal_t sg = ring_.sig[(size_t)(k % S)];
+      SdmaEngine::arm(sg, eng.parts((size_t)h.copied, 1));
+      eng.copy_d2h(lay_.slot(ring_.p, k), from, (size_t)h.copied, sg, 1);
+      st_.d2h_bytes += h.copied;
+      st_.pieces++;
+      ++(h.packed ? st_.packed_pieces : st_.raw_pieces);
+    };
+    if (pack)
+      for (int64_t j = 0; j < std::min<int64_t>(groups, 2); ++j) pack_group(j);
+    for (int64_t k = 0; k < std::min<int64_t>(np, S); ++k) issue(k);
+    for (int64_t k = 0; k < np; ++k) {
+      const double a = now_ms();
+      SdmaEngine::wait(ring_.sig[(size_t)(k % S)]);
+      st_.d2h_wait_ms += now_ms() - a;
+      // the last piece of group j has landed, and every piece before it was waited for: its half of the
+      // device ring takes group j + 2
+      if (pack && k % S == S - 1 && k / S + 2 < groups) pack_group(k / S + 2);
+      const Held& h = held_[(size_t)(k % S)];
+      FixedPiece p;
+      p.base = lay_.slot(ring_.p, k);
+      p.copied = h.copied;
+      p.record_bytes = std::min(piece, bytes - k * piece);
+      p.packed = h.packed;
+      p.last = last_round && k == np - 1;
+      deliver(p);
+      if (k + S < np) issue(k + S);
+    }
+    st_.bytes += bytes;
+    if (last_round && !eof_sent_) eof_only();  // a last round without records
+  }
+
+  // the task's EOF marker in a buffer of its own
+  void eof_only() {
+    FixedPiece p;
+    p.last = true;
+    deliver(p);
+  }
+
+ private:
+  struct Held {
+    int64_t copied = 0;
+    bool packed = false;
+  };
+  ColpackResult* host_results() const {  // behind the 2 * slots descriptors
+    return reinterpret_cast<ColpackResult*>(ws_.h_pk->as<ColpackPieceDesc>() + 2 * lay_.slots);
+  }
+  void deliver(const FixedPiece& p) {
+    FixedDeliveryCounters c;
+    c.eof_sent = eof_sent_;
+    deliver_fixed_piece(p, lay_.buf_bytes, lay_.kv_buf_bytes, bufs_, sink_, &c);
+    eof_sent_ = c.eof_sent;
+    st_.buffers += c.buffers;
+    st_.sink_ms += c.sink_ms;
+    st_.unpack_ms += c.unpack_ms;
+  }
+  const FixedLayout lay_;
+  FixedWs& ws_;
+  DeviceReduceStats& st_;
+  const FixedSink& sink_;
+  Ring ring_;
+  std::vector<uint8_t> tail_;
+  std::vector<Held> held_;
+  FixedBuffers bufs_;
+  bool eof_sent_ = false;
+};
 }  // namespace
 
-int64_t fixed_round_ws_bytes(int64_t round_bytes, int runs) {
+int64_t fixed_round_ws_bytes(int64_t round_bytes, int runs, const DeviceReduceConfig* cfg) {
   // two output slots grown 1/8 past a round that may run ~10 % over the mean, plus the merger's
   // per-round plan tables (cell splits, samples: ~2 % of the round) and its upload slots
   const double slot = (double)round_bytes * 1.1 * 1.125;
-  return (int64_t)(2 * slot + 0.02 * (double)round_bytes) + (int64_t)runs * 4096 + (16ll << 20);
+  int64_t packed = 0;
+  if (cfg && cfg->pack_version != 0) {  // the device ring of packed pieces with its tables, grown the same way
+    const FixedLayout lay = fixed_layout(cfg->kv_buf_bytes, cfg->piece_bytes, cfg->pinned_slots, cfg->pack_version);
+    const PackNeed n = pack_need(lay, (int64_t)((double)round_bytes * 1.1) / kTeraRecordBytes + 1);
+    packed = n.ring + n.desc + n.res + n.table;
+    packed += packed / 8;
+  }
+  return (int64_t)(2 * slot + 0.02 * (double)round_bytes) + packed + (int64_t)runs * 4096 + (16ll << 20);
 }
 
 void prewarm_device_reduce(const DeviceReduceConfig& cfg, int runs, int count) {
   HIP_CHECK(hipSetDevice(cfg.device));
   const int64_t rec = std::max<int64_t>(1, cfg.round_bytes / kTeraRecordBytes);
   const int64_t mr = rec + rec / 8;  // rounds run a little over their mean
-  const int64_t buf_bytes = std::max<int64_t>(1, cfg.kv_buf_bytes / kTeraRecordBytes) * kTeraRecordBytes;
-  const int64_t piece = std::max<int64_t>(1, cfg.piece_bytes / buf_bytes) * buf_bytes;
-  const int S = std::max(2, cfg.pinned_slots);
+  // the ring block a task with this configuration asks for (the engine caches blocks by exact size)
+  const FixedLayout lay = fixed_layout(cfg.kv_buf_bytes, cfg.piece_bytes, cfg.pinned_slots, cfg.pack_version);
   // `count` workspaces and rings held at once, so the pools keep that many for concurrent tasks
   std::vector<std::unique_ptr<WsLease>> leases;
   std::vector<std::unique_ptr<Ring>> rings;
@@ -224,7 +430,7 @@ void prewarm_device_reduce(const DeviceReduceConfig& cfg, int runs, int count) {
     leases.push_back(std::make_unique<WsLease>(cfg.device));
     FixedWs& ws = *leases.back()->w;
     if (!ws.merger || ws.merger->max_records() < mr || ws.merger->max_runs() < runs) ws.merger.reset(new DeviceMerger(mr, runs));
-    rings.push_back(std::make_unique<Ring>(SdmaEngine::for_device(cfg.device), (size_t)piece * S, S));
+    rings.push_back(std::make_unique<Ring>(SdmaEngine::for_device(cfg.device), lay.ring_bytes, lay.slots));
   }
   rings.clear();  // back to the engine's cache
   for (auto& l : leases) l->clean = true;
@@ -271,19 +477,13 @@ DeviceReduceStats device_reduce_fixed(const DeviceReduceConfig& cfg, const std::
   WsLease lease(cfg.device, N * kTeraRecordBytes);
   FixedWs& ws = *lease.w;
   hipStream_t s = ws.s;
-  const int64_t buf_records = std::max<int64_t>(1, cfg.kv_buf_bytes / kTeraRecordBytes);
-  const int64_t buf_bytes = buf_records * kTeraRecordBytes;
-  const int64_t piece = std::max<int64_t>(1, cfg.piece_bytes / buf_bytes) * buf_bytes;
-  std::vector<uint8_t> tail((size_t)cfg.kv_buf_bytes + 16);
-  auto emit = [&](const uint8_t* p, int64_t len) {
+  const FixedLayout lay = fixed_layout(cfg.kv_buf_bytes, cfg.piece_bytes, cfg.pinned_slots, cfg.pack_version);
+  if (N == 0) {  // the EOF marker alone: nothing to merge, pack or copy
+    const uint8_t eof[2] = {0xFF, 0xFF};
     const double a = now_ms();
-    if (sink(p, len) != 0) throw std::runtime_error("dataFromUda callback failed");
+    if (sink(eof, kEofBytes) != 0) throw std::runtime_error("dataFromUda callback failed");
     st.sink_ms += now_ms() - a;
     st.buffers++;
-  };
-  if (N == 0) {
-    tail[0] = tail[1] = 0xFF;
-    emit(tail.data(), kEofBytes);
     lease.clean = true;
     return st;
   }
@@ -298,8 +498,8 @@ DeviceReduceStats device_reduce_fixed(const DeviceReduceConfig& cfg, const std::
       // what this task allocates beyond the workspace's buffers that are already large enough (a pooled
       // workspace's other buffers do not shrink what a grown one takes: alloc frees, then allocates anew)
       const int64_t r = std::min(rb, N * kTeraRecordBytes), slot = (int64_t)((double)r * 1.1);
-      return FixedWs::grow(ws.out[0], slot) + FixedWs::grow(ws.out[1], slot) + (int64_t)(0.02 * (double)r) + (int64_t)K * 4096 +
-             (16ll << 20);
+      return FixedWs::grow(ws.out[0], slot) + FixedWs::grow(ws.out[1], slot) +
+             pack_grow(ws, lay, slot / kTeraRecordBytes + 1) + (int64_t)(0.02 * (double)r) + (int64_t)K * 4096 + (16ll << 20);
     };
     const int64_t hr = led.headroom(cfg.device);
     while (round_bytes > (64ll << 20) && need(round_bytes) > hr) round_bytes /= 2;
@@ -382,11 +582,11 @@ DeviceReduceStats device_reduce_fixed(const DeviceReduceConfig& cfg, const std::
   DeviceMerger& merger = *ws.merger;
   DeviceBuffer* out = ws.out;
   for (int i = 0; i < 2; ++i) FixedWs::ensure(out[i], (size_t)std::max<int64_t>(max_round, 1) * kTeraRecordBytes);
+  pack_ensure(ws, lay, max_round);
   struct {
     hipEvent_t* e;
   } merged{ws.merged};
-  const int S = std::max(2, cfg.pinned_slots);
-  Ring ring(SdmaEngine::for_device(cfg.device), (size_t)piece * S, S);
+  FixedDelivery delivery(cfg, lay, ws, st, sink);
   st.plan_ms = now_ms() - t0;
 
   auto enqueue_merge = [&](int q) {
@@ -402,46 +602,7 @@ DeviceReduceStats device_reduce_fixed(const DeviceReduceConfig& cfg, const std::
     st.merge_passes = std::max(st.merge_passes, merger.last_passes());
     HIP_CHECK(hipEventRecord(merged.e[q % 2], s));
   };
-  SdmaEngine& eng = ring.eng;
-  auto deliver_round = [&](int q) {
-    const uint8_t* src = out[q % 2].as<uint8_t>();
-    const int64_t bytes = round_recs[q] * kTeraRecordBytes;
-    const bool last_round = q == Q - 1;
-    const int64_t np = (bytes + piece - 1) / piece;
-    auto issue = [&](int64_t k) {
-      const int64_t off = k * piece, len = std::min(piece, bytes - off);
-      hsa_signal_t sg = ring.sig[(size_t)(k % S)];
-      SdmaEngine::arm(sg, eng.parts((size_t)len, 1));
-      eng.copy_d2h(ring.p + (k % S) * piece, src + off, (size_t)len, sg, 1);
-    };
-    for (int64_t k = 0; k < std::min<int64_t>(np, S); ++k) issue(k);
-    bool eof_sent = false;
-    for (int64_t k = 0; k < np; ++k) {
-      const double a = now_ms();
-      SdmaEngine::wait(ring.sig[(size_t)(k % S)]);
-      st.d2h_wait_ms += now_ms() - a;
-      const uint8_t* base = ring.p + (k % S) * piece;
-      const int64_t plen = std::min(piece, bytes - k * piece);
-      for (int64_t off = 0; off < plen; off += buf_bytes) {
-        const int64_t len = std::min(buf_bytes, plen - off);
-        const bool final_chunk = last_round && k == np - 1 && off + len >= plen;
-        if (final_chunk && len + kEofBytes <= cfg.kv_buf_bytes) {
-          std::memcpy(tail.data(), base + off, (size_t)len);
-          tail[(size_t)len] = tail[(size_t)len + 1] = 0xFF;
-          emit(tail.data(), len + kEofBytes);
-          eof_sent = true;
-        } else {
-          emit(base + off, len);
-        }
-      }
-      if (k + S < np) issue(k + S);
-    }
-    st.bytes += bytes;
-    if (last_round && !eof_sent) {
-      tail[0] = tail[1] = 0xFF;
-      emit(tail.data(), kEofBytes);
-    }
-  };
+  auto deliver_round = [&](int q) { delivery.deliver_round(q, round_recs[q], q == Q - 1); };
 
   enqueue_merge(0);
   for (int q = 0; q < Q; ++q) {
@@ -586,6 +747,7 @@ DeviceReduceStats device_reduce_fixed_blocks(const DeviceReduceConfig& cfg, int 
     return st;
   }
   // ---- rounds: bounds from the block keys, each round's block range and input layout per stream
+  const FixedLayout lay = fixed_layout(cfg.kv_buf_bytes, cfg.piece_bytes, cfg.pinned_slots, cfg.pack_version);
   HbmLedger& led = HbmLedger::get();
   int64_t round_bytes = std::max<int64_t>(cfg.round_bytes, kTeraRecordBytes);
   struct Span {
@@ -651,6 +813,7 @@ DeviceReduceStats device_reduce_fixed_blocks(const DeviceReduceConfig& cfg, int 
     const int64_t ob = std::max<int64_t>(mr, 1) * kTeraRecordBytes, db = std::max<int64_t>(NB, 1) * (int64_t)sizeof(DecodeDesc);
     return FixedWs::grow(ws.in[0], std::max<int64_t>(mi, 256)) + FixedWs::grow(ws.in[1], std::max<int64_t>(mi, 256)) +
            FixedWs::grow(ws.out[0], ob) + FixedWs::grow(ws.out[1], ob) + FixedWs::grow(ws.d_descs[0], db) + FixedWs::grow(ws.d_descs[1], db) +
+           pack_grow(ws, lay, std::max<int64_t>(mr, 1)) +
            (int64_t)(0.02 * (double)ob) + (int64_t)K * 4096 + (16ll << 20);
   };
   std::unique_ptr<HbmLedger::Reservation> res;
@@ -673,6 +836,7 @@ DeviceReduceStats device_reduce_fixed_blocks(const DeviceReduceConfig& cfg, int 
   for (auto& b : ws.in) FixedWs::ensure(b, (size_t)std::max<int64_t>(max_in, 256));
   for (auto& b : ws.out) FixedWs::ensure(b, (size_t)std::max<int64_t>(max_recs, 1) * kTeraRecordBytes);
   for (auto& b : ws.d_descs) FixedWs::ensure(b, (size_t)std::max<int64_t>(NB, 1) * sizeof(DecodeDesc));
+  pack_ensure(ws, lay, std::max<int64_t>(max_recs, 1));
   FixedWs::ensure(ws.d_bases, 2 * (size_t)K * sizeof(uint8_t*));
   FixedWs::ensure(ws.d_nrec, 2 * (size_t)K * 8);
   FixedWs::ensure(ws.d_bset, (size_t)K * sizeof(int));
@@ -687,18 +851,7 @@ DeviceReduceStats device_reduce_fixed_blocks(const DeviceReduceConfig& cfg, int 
   }
   DeviceMerger& merger = *ws.merger;
   st.rounds = Q;
-  const int64_t buf_records = std::max<int64_t>(1, cfg.kv_buf_bytes / kTeraRecordBytes);
-  const int64_t buf_bytes = buf_records * kTeraRecordBytes;
-  const int64_t piece = std::max<int64_t>(1, cfg.piece_bytes / buf_bytes) * buf_bytes;
-  const int SL = std::max(2, cfg.pinned_slots);
-  Ring ring(SdmaEngine::for_device(cfg.device), (size_t)piece * SL, SL);
-  std::vector<uint8_t> tail((size_t)cfg.kv_buf_bytes + 16);
-  auto emit = [&](const uint8_t* p, int64_t len) {
-    const double a = now_ms();
-    if (sink(p, len) != 0) throw std::runtime_error("dataFromUda callback failed");
-    st.sink_ms += now_ms() - a;
-    st.buffers++;
-  };
+  FixedDelivery delivery(cfg, lay, ws, st, sink);
   if (!ws.ds) HIP_CHECK(hipStreamCreateWithFlags(&ws.ds, hipStreamNonBlocking));
   // the prefix pass and this task's earlier use of the buffers (on s) come first
   hipEvent_t planned = nullptr;
@@ -781,47 +934,7 @@ DeviceReduceStats device_reduce_fixed_blocks(const DeviceReduceConfig& cfg, int 
     st.merge_passes = std::max(st.merge_passes, merger.last_passes());
     HIP_CHECK(hipEventRecord(ws.merged[par], s));
   };
-  SdmaEngine& eng = ring.eng;
-  bool eof_sent = false;
-  auto deliver_round = [&](int q) {
-    const uint8_t* src = ws.out[q & 1].as<uint8_t>();
-    const int64_t bytes = round_recs[(size_t)q] * kTeraRecordBytes;
-    const bool last_round = q == Q - 1;
-    const int64_t np = (bytes + piece - 1) / piece;
-    auto issue = [&](int64_t k) {
-      const int64_t off = k * piece, len = std::min(piece, bytes - off);
-      hsa_signal_t sg = ring.sig[(size_t)(k % SL)];
-      SdmaEngine::arm(sg, eng.parts((size_t)len, 1));
-      eng.copy_d2h(ring.p + (k % SL) * piece, src + off, (size_t)len, sg, 1);
-    };
-    for (int64_t k = 0; k < std::min<int64_t>(np, SL); ++k) issue(k);
-    for (int64_t k = 0; k < np; ++k) {
-      const double a = now_ms();
-      SdmaEngine::wait(ring.sig[(size_t)(k % SL)]);
-      st.d2h_wait_ms += now_ms() - a;
-      const uint8_t* base = ring.p + (k % SL) * piece;
-      const int64_t plen = std::min(piece, bytes - k * piece);
-      for (int64_t off = 0; off < plen; off += buf_bytes) {
-        const int64_t len = std::min(buf_bytes, plen - off);
-        const bool final_chunk = last_round && k == np - 1 && off + len >= plen;
-        if (final_chunk && len + kEofBytes <= cfg.kv_buf_bytes) {
-          std::memcpy(tail.data(), base + off, (size_t)len);
-          tail[(size_t)len] = tail[(size_t)len + 1] = 0xFF;
-          emit(tail.data(), len + kEofBytes);
-          eof_sent = true;
-        } else {
-          emit(base + off, len);
-        }
-      }
-      if (k + SL < np) issue(k + SL);
-    }
-    st.bytes += bytes;
-    if (last_round && !eof_sent) {
-      tail[0] = tail[1] = 0xFF;
-      emit(tail.data(), kEofBytes);
-      eof_sent = true;
-    }
-  };
+  auto deliver_round = [&](int q) { delivery.deliver_round(q, round_recs[(size_t)q], q == Q - 1); };
   // Rounds are delivered by a thread of their own, in order, while this one decodes, cuts and merges the
   // next: enqueue_round waits for its split positions (a stream sync that also covers the previous
   // round's merge), which in one thread held the round before it back from the link. Round q reuses

@@ -8,7 +8,8 @@
 // stays bounded: a key sample gives Q-1 bounds, every run is split at them on the device, and round
 // q merges the q-th slice of every run (F2 -> F3 -> F4) into one of two output slots while the host
 // delivers round q-1: SDMA pieces into a pinned ring, cut into <= kv_buf whole-record buffers handed
-// to the sink, the last one carrying the IFile EOF marker.
+// to the sink, the last one carrying the IFile EOF marker. With DeviceReduceConfig::pack_version the
+// pieces cross the link bit-packed (colpack) and are unpacked on the host (fixed_delivery.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,6 +29,12 @@ struct DeviceReduceConfig {
   int64_t round_bytes = 2ll << 30;    // target merged bytes per round (two output slots of this size)
   int64_t piece_bytes = 64ll << 20;   // D2H granule
   int pinned_slots = 4;
+  // Bit-pack each D2H piece per column on the device before its copy (codec/colpack.h) and unpack it on
+  // the host right before the sink: 0 off, 1 colpack version 1, 2 version 2 (key differences,
+  // bit-contiguous rows). The sink's buffers are the same either way; packed, a device ring of
+  // 2 * pinned_slots piece regions holds the packed pieces, and the pinned ring block carries two unpack
+  // staging buffers.
+  int pack_version = 0;
   int64_t sample_every = 4096;        // one key sampled per this many records for the round bounds
   // HBM admission (hbm_ledger.h): the task's round working set is reserved before its merge; a
   // round that could never fit the budget is halved until it does. A reservation already bound to
@@ -52,6 +59,13 @@ struct DeviceReduceStats {
   int64_t hbm_reserved = 0;    // bytes reserved for the round working set
   int64_t round_bytes = 0;     // round size used (after any shrink to fit the budget)
   int64_t decoded_blocks = 0;  // device_reduce_fixed_blocks: blocks decoded over all rounds
+  int64_t d2h_bytes = 0;       // bytes that crossed the link for `bytes` (equal with pack_version 0)
+  int64_t pieces = 0;          // D2H pieces = packed_pieces + raw_pieces
+  int64_t packed_pieces = 0;   // sent bit-packed
+  int64_t raw_pieces = 0;      // sent as records (pack off, or a piece whose stride would exceed 0.9 of a record)
+  int64_t delta_pieces = 0;    // packed pieces whose key columns hold key differences (version 2)
+  double unpack_ms = 0;        // host unpack of the packed pieces
+  double pack_wait_ms = 0;     // waiting for a group of pieces to be packed on the device
 };
 
 // Build what a FIXED10 task's first round would otherwise build on its critical path (a fresh reduce
@@ -62,8 +76,9 @@ struct DeviceReduceStats {
 void prewarm_device_reduce(const DeviceReduceConfig& cfg, int runs, int count = 1);
 
 // HBM a FIXED10 round working set of `round_bytes` merged bytes needs (two output slots and the
-// merger's per-round tables), for admission.
-int64_t fixed_round_ws_bytes(int64_t round_bytes, int runs);
+// merger's per-round tables; with cfg->pack_version != 0 the device ring of packed pieces as well), for
+// admission.
+int64_t fixed_round_ws_bytes(int64_t round_bytes, int runs, const DeviceReduceConfig* cfg = nullptr);
 
 // True if every run holds whole TeraSort-shaped records (VInt 11, VInt 91, Text 10 + 90 bytes).
 // Synchronizes `s`.

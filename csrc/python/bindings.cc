@@ -19,6 +19,8 @@
 #include "block_decoder.h"
 #include "device_engine.h"
 #include "device_ptr.h"
+#include "device_reduce.h"
+#include "fixed_delivery.h"
 #include "mof_cache.h"
 #include "consumer/reduce_task.h"
 #include "service/merge_service.h"
@@ -479,6 +481,104 @@ PYBIND11_MODULE(_uda_native, m) {
     return gpu_encode(pieces, L, buf_records, device, 2, key_off, key_len);
   }, py::arg("pieces"), py::arg("record_bytes"), py::arg("buf_records"), py::arg("key_off"), py::arg("key_len"),
      py::arg("device") = 0);
+  // FIXED10 delivery (gpu/fixed_delivery.h, gpu/device_reduce.h)
+  // The buffers the host side of the delivery hands the sink for one landed piece. No GPU.
+  m.def("fixed_delivery_piece", [](py::bytes piece, int64_t record_bytes, int64_t buf_bytes, int64_t kv_buf, bool packed,
+                                   bool last) {
+    std::string s = piece;
+    if (kv_buf < 1 || buf_bytes < 1) throw py::value_error("fixed_delivery_piece: bad buffer sizes");
+    const size_t one = (size_t)std::max(kv_buf, buf_bytes) + 16;
+    std::vector<uint8_t> stg(2 * one), tail(one);
+    gpu::FixedBuffers bufs;
+    bufs.staging[0] = stg.data();
+    bufs.staging[1] = stg.data() + one;
+    bufs.tail = tail.data();
+    gpu::FixedPiece p;
+    p.base = (const uint8_t*)s.data();
+    p.copied = (int64_t)s.size();
+    p.record_bytes = record_bytes;
+    p.packed = packed;
+    p.last = last;
+    std::vector<std::string> out;
+    gpu::FixedDeliveryCounters c;
+    gpu::deliver_fixed_piece(p, buf_bytes, kv_buf, bufs, [&](const uint8_t* b, int64_t len) {
+      out.emplace_back((const char*)b, (size_t)len);
+      return 0;
+    }, &c);
+    py::list ret;
+    for (const auto& b : out) ret.append(py::bytes(b));
+    return ret;
+  }, py::arg("piece"), py::arg("record_bytes"), py::arg("buf_bytes"), py::arg("kv_buf"), py::arg("packed"), py::arg("last"));
+  m.def("delivery_pack_version", &gpu::delivery_pack_version);
+  m.def("fixed_delivery_layout", [](int64_t kv_buf, int64_t piece_bytes, int pinned_slots, int pack_version) {
+    const gpu::FixedLayout l = gpu::fixed_layout(kv_buf, piece_bytes, pinned_slots, pack_version);
+    py::dict d;
+    d["buf_records"] = l.buf_records;
+    d["piece"] = l.piece;
+    d["slots"] = l.slots;
+    d["slot_bytes"] = l.slot_bytes;
+    d["region_bytes"] = l.region_bytes;
+    d["staging_bytes"] = l.staging_bytes;
+    d["ring_bytes"] = (int64_t)l.ring_bytes;
+    d["bound_full"] = pack_version ? l.piece_bound(l.piece_recs) : 0;
+    return d;
+  });
+  // Upload `runs` (sorted FIXED10 records), run device_reduce_fixed over them and return the delivered
+  // buffers with the run's statistics. pack: mapred.uda.gpu.delivery.pack's values.
+  m.def("gpu_device_reduce_fixed", [](const std::vector<std::string>& runs, int64_t kv_buf, int64_t round_bytes,
+                                      int64_t piece_bytes, const std::string& pack, int device) {
+    gpu::DeviceReduceConfig cfg;
+    cfg.device = device;
+    cfg.kv_buf_bytes = kv_buf;
+    cfg.round_bytes = round_bytes;
+    cfg.piece_bytes = piece_bytes;
+    cfg.sample_every = 16;
+    cfg.pack_version = gpu::delivery_pack_version(pack);
+    if (cfg.pack_version < 0) throw py::value_error("gpu_device_reduce_fixed: pack is auto, v1 or off");
+    if (kv_buf < 1 || round_bytes < 1 || piece_bytes < 1) throw py::value_error("gpu_device_reduce_fixed: bad sizes");
+    for (const auto& r : runs)
+      if (r.size() % (size_t)gpu::kTeraRecordBytes) throw py::value_error("gpu_device_reduce_fixed: need whole records");
+    std::vector<std::string> out;
+    gpu::DeviceReduceStats st;
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      std::vector<gpu::DeviceBuffer> dev(runs.size());
+      std::vector<gpu::RunDesc> rd(runs.size());
+      for (size_t i = 0; i < runs.size(); ++i) {
+        dev[i].alloc(std::max<size_t>(runs[i].size(), 16));
+        if (!runs[i].empty()) HIP_CHECK(hipMemcpy(dev[i].as(), runs[i].data(), runs[i].size(), hipMemcpyHostToDevice));
+        rd[i].base = dev[i].as<uint8_t>();
+        rd[i].nbytes = (int64_t)runs[i].size();
+        rd[i].nrec = rd[i].nbytes / gpu::kTeraRecordBytes;
+        rd[i].offsets = nullptr;
+      }
+      st = gpu::device_reduce_fixed(cfg, rd, [&](const uint8_t* b, int64_t len) {
+        out.emplace_back((const char*)b, (size_t)len);
+        return 0;
+      });
+    }
+    py::list bufs;
+    for (const auto& b : out) bufs.append(py::bytes(b));
+    py::dict d;
+    d["records"] = st.records;
+    d["bytes"] = st.bytes;
+    d["buffers"] = st.buffers;
+    d["rounds"] = st.rounds;
+    d["round_bytes"] = st.round_bytes;
+    d["hbm_reserved"] = st.hbm_reserved;
+    d["d2h_bytes"] = st.d2h_bytes;
+    d["pieces"] = st.pieces;
+    d["packed_pieces"] = st.packed_pieces;
+    d["raw_pieces"] = st.raw_pieces;
+    d["delta_pieces"] = st.delta_pieces;
+    d["unpack_ms"] = st.unpack_ms;
+    d["pack_wait_ms"] = st.pack_wait_ms;
+    d["d2h_wait_ms"] = st.d2h_wait_ms;
+    d["sink_ms"] = st.sink_ms;
+    return py::make_tuple(bufs, d);
+  }, py::arg("runs"), py::arg("kv_buf"), py::arg("round_bytes"), py::arg("piece_bytes") = 64ll << 20,
+     py::arg("pack") = "auto", py::arg("device") = 0);
   m.def("codec_from_class", [](const std::string& c) {
     bool unsup = false;
     int v = (int)codec_from_class(c, &unsup);
