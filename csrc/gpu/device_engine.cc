@@ -1,6 +1,5 @@
 // Device shuffle/merge engine implementation. See device_engine.h for the design.
 #include "device_engine.h"
-#include "codec/colpack.h"
 #include "device_ptr.h"
 #include "hbm_ledger.h"
 #include "merge_plan.h"
@@ -768,13 +767,11 @@ ShuffleJob::ShuffleJob(const ShuffleConfig& cfg) : cfg_(cfg) {
   if (cfg_.d2h != "sdma" && cfg_.d2h != "hip") throw std::runtime_error("ShuffleJob: d2h must be sdma or hip");
   if (cfg_.store != "hbm" && cfg_.store != "host" && cfg_.store != "disk")
     throw std::runtime_error("unknown store tier " + cfg_.store);
-  if (cfg_.delivery_pack != "auto" && cfg_.delivery_pack != "v1" && cfg_.delivery_pack != "off")
-    throw std::runtime_error("ShuffleJob: delivery_pack must be auto, v1 or off");
+  const int version = delivery_pack_version(cfg_.delivery_pack);
+  if (version < 0) throw std::runtime_error("ShuffleJob: delivery_pack must be auto, v1 or off");
   check_delivery_order(cfg_.delivery_order);
-  pack_ = cfg_.deliver_host && cfg_.delivery_pack != "off";
-  pack_version_ = cfg_.delivery_pack == "v1" ? (int)kColpackVersion : (int)kColpackVersion2;
-  if (const char* e = std::getenv("UDA_DELIVERY_PACK"))
-    if (std::atoi(e) == 0) pack_ = false;
+  pack_ = cfg_.deliver_host && version != 0;
+  lay_ = fixed_layout(cfg_.kv_buf_bytes, cfg_.d2h_piece_bytes, cfg_.pinned_slots, pack_ ? version : 0);
   R_ = cfg_.reducers;
   Q_ = cfg_.rounds;
   C_ = R_ * Q_;
@@ -791,11 +788,6 @@ ShuffleJob::ShuffleJob(const ShuffleConfig& cfg) : cfg_(cfg) {
   HIP_CHECK(hipStreamCreateWithPriority(&s_compute_, hipStreamNonBlocking, spill ? hi_prio : lo_prio));
   HIP_CHECK(hipStreamCreateWithFlags(&s_copy_, hipStreamNonBlocking));
   HIP_CHECK(hipStreamCreateWithFlags(&s_plan_, hipStreamNonBlocking));
-  buf_records_ = std::max<int64_t>(1, cfg_.kv_buf_bytes / kTeraRecordBytes);
-  const int64_t buf_bytes = buf_records_ * kTeraRecordBytes;
-  piece_bytes_ = std::max<int64_t>(1, cfg_.d2h_piece_bytes / buf_bytes) * buf_bytes;
-  // a packed piece of few records is longer than the records themselves (header, padding)
-  ring_stride_ = pack_ ? std::max(piece_bytes_, pack_bound(piece_bytes_ / kTeraRecordBytes)) : piece_bytes_;
   merged_ev_.resize(kSlots);
   comm_ev_.resize(kSlots);
   sent_ev_.resize(2);
@@ -860,7 +852,7 @@ std::string ShuffleJob::delivery_name() const {
   std::string name = sdma_ ? sdma_->describe() : "hip[numa=" + std::to_string(device_numa_node(cfg_.device)) + "]";
   name += " ring=" + ring_numa_ + " order=" + cfg_.delivery_order;
   if (!pack_) return name + " pack=off";
-  name += " pack=colbits v" + std::to_string(pack_version_);
+  name += " pack=colbits v" + std::to_string(lay_.pack_version);
   if (last_delta_ >= 0) name += last_delta_ ? " delta" : " plain";  // the last step's pieces
   if (last_d2h_ratio_ >= 0) {  // the last step's d2h_bytes / bytes_in
     char b[32];
@@ -870,18 +862,13 @@ std::string ShuffleJob::delivery_name() const {
   return name;
 }
 
-int64_t ShuffleJob::pack_bound(int64_t nrec) const {
-  return pack_version_ == (int)kColpackVersion ? colpack_bound(kTeraRecordBytes, nrec)
-                                               : colpack2_bound(kTeraRecordBytes, nrec, buf_records_);
-}
-
 std::vector<ShuffleJob::PackPiece> ShuffleJob::round_pieces(const std::vector<int64_t>& group_recs) const {
   std::vector<PackPiece> v;
   int64_t doff = 0;
-  for (const DeliveryPiece& dp : delivery_schedule(group_recs, piece_bytes_, "reducer", kTeraRecordBytes)) {
+  for (const DeliveryPiece& dp : delivery_schedule(group_recs, lay_.piece, "reducer", kTeraRecordBytes)) {
     const int64_t nrec = dp.len / kTeraRecordBytes;
     v.push_back(PackPiece{dp.src_off, doff, nrec});
-    doff += pack_bound(nrec);
+    doff += lay_.piece_bound(nrec);
   }
   return v;
 }
@@ -1361,7 +1348,7 @@ void ShuffleJob::compute_plans() {
       max_pieces = std::max(max_pieces, pack_n_[q]);
       for (const PackPiece& pc : pieces[q]) {
         pack_max_nrec_[q] = std::max(pack_max_nrec_[q], pc.nrec);
-        packed_bytes = std::max(packed_bytes, pc.dst_off + pack_bound(pc.nrec));
+        packed_bytes = std::max(packed_bytes, pc.dst_off + lay_.piece_bound(pc.nrec));
       }
     }
     packed_slots_.resize(kSlots);
@@ -1381,7 +1368,7 @@ void ShuffleJob::compute_plans() {
       std::vector<ColpackPieceDesc> v;
       int wave0 = 0;
       for (const DeliveryPiece& dp :
-           delivery_schedule(plans_[q].group_recs, piece_bytes_, cfg_.delivery_order, kTeraRecordBytes)) {
+           delivery_schedule(plans_[q].group_recs, lay_.piece, cfg_.delivery_order, kTeraRecordBytes)) {
         const PackPiece& pc = pieces[q][(size_t)dp.pack_index];
         v.push_back(ColpackPieceDesc{out_slots_[q % kSlots].as<uint8_t>() + pc.src_off,
                                      packed_slots_[q % kSlots].as<uint8_t>() + pc.dst_off, pc.nrec});
@@ -1535,7 +1522,7 @@ void ShuffleJob::plan() {
   HIP_CHECK(hipSetDevice(cfg_.device));
   compute_plans();
   if (cfg_.deliver_host && !copy_thr_.joinable()) {
-    const size_t ring_bytes = (size_t)ring_stride_ * cfg_.pinned_slots;
+    const size_t ring_bytes = (size_t)lay_.slot_bytes * lay_.slots;
     if (cfg_.d2h == "sdma") {
       sdma_.reset(new SdmaEngine(cfg_.device));
       ring_ = static_cast<uint8_t*>(sdma_->alloc_host(ring_bytes));
@@ -1557,7 +1544,7 @@ void ShuffleJob::plan() {
     for (int i = 0; i < R_; ++i) eof_bufs_.emplace_back(new uint8_t[(size_t)cfg_.kv_buf_bytes + 16]);
     unpack_bufs_.clear();
     if (pack_) {
-      const size_t one = (size_t)std::max(cfg_.kv_buf_bytes, buf_records_ * kTeraRecordBytes) + 16;
+      const size_t one = (size_t)std::max(cfg_.kv_buf_bytes, lay_.buf_bytes) + 16;
       for (int i = 0; i < R_; ++i) unpack_bufs_.emplace_back(new uint8_t[2 * one]);
     }
     copy_thr_ = std::thread([this] { name_thread("uda-copy"); copy_loop(); });
@@ -1637,7 +1624,7 @@ void ShuffleJob::copy_loop() {
       // to an issued piece whose consumer reaches it without needing another slot, so no order can deadlock.
       int issued = 0;
       for (const DeliveryPiece& dp :
-           delivery_schedule(r.group_recs, piece_bytes_, cfg_.delivery_order, kTeraRecordBytes)) {
+           delivery_schedule(r.group_recs, lay_.piece, cfg_.delivery_order, kTeraRecordBytes)) {
         if (r.early > 0 && issued == r.early) HIP_CHECK(hipEventSynchronize(merged_ev_[r.slot]));  // the rest is packed
         int k = -1;
         {
@@ -1661,7 +1648,7 @@ void ShuffleJob::copy_loop() {
             }
           pinned_free_[k] = false;
         }
-        uint8_t* dst = ring_ + (int64_t)k * ring_stride_;
+        uint8_t* dst = lay_.slot(ring_, k);
         const uint8_t* from = src + dp.src_off;
         int64_t copy_len = dp.len;
         bool packed = false;
@@ -1672,10 +1659,8 @@ void ShuffleJob::copy_loop() {
             throw std::runtime_error("delivery_pack: piece list out of step with the copy loop");
           const ColpackResult pr = pres[issued];
           if (pr.packed) {
-            if (pr.bytes < (int64_t)kColpackHeaderBytes || pr.bytes > pack_bound(ppieces[pi].nrec))
-              throw std::runtime_error("delivery_pack: packed length outside the piece's region");
             packed = true;
-            copy_len = pr.bytes;
+            copy_len = lay_.packed_copy_len(pr.bytes, ppieces[pi].nrec);
             from = packed_slots_[r.slot].as<uint8_t>() + ppieces[pi].dst_off;
           }
         }
@@ -1727,16 +1712,19 @@ void ShuffleJob::copy_loop() {
   }
 }
 
-// Consumer thread of reducer i: the "Java side" hand-off. Buffers hold whole records and are at
-// most kv_buf_bytes; the reducer's final buffer carries the IFile EOF marker (-1, -1).
+// Consumer thread of reducer i: the "Java side" hand-off. Every item is one landed piece (or the EOF
+// alone) for deliver_fixed_piece (fixed_delivery.h): buffers of whole records, at most kv_buf_bytes, the
+// reducer's final one carrying the IFile EOF marker (-1, -1).
 void ShuffleJob::consume_loop(int i) {
   try {
     bind_thread_to_cpus(device_consumer_cpus(cfg_.device));
     HIP_CHECK(hipSetDevice(cfg_.device));
-    const int64_t buf_bytes = buf_records_ * kTeraRecordBytes;
-    uint8_t* eb = eof_bufs_[i].get();
-    const size_t unpack_one = (size_t)std::max(cfg_.kv_buf_bytes, buf_bytes) + 16;
-    int64_t unpack_turn = 0;  // the two staging buffers alternate
+    FixedBuffers bufs;
+    bufs.tail = eof_bufs_[i].get();
+    if (pack_) {
+      bufs.staging[0] = unpack_bufs_[i].get();
+      bufs.staging[1] = bufs.staging[0] + (size_t)std::max(cfg_.kv_buf_bytes, lay_.buf_bytes) + 16;
+    }
     for (;;) {
       Item it;
       bool check;
@@ -1748,12 +1736,9 @@ void ShuffleJob::consume_loop(int i) {
         items_[i].pop_front();
         check = step_check_delivery_;
       }
-      uint64_t got_ck = 0;
-      int err = 0;
-      int64_t nb = 0;
       double waited = 0;
-      bool eof_sent = false;
-      double unpack_ms = 0;
+      FixedPiece p;  // an EOF-only item: no records, only `last`
+      p.last = it.last;
       if (it.pslot >= 0) {
         if (sdma_)
           SdmaEngine::wait(piece_sig_[it.pslot]);
@@ -1765,65 +1750,35 @@ void ShuffleJob::consume_loop(int i) {
           note_landing(it.pslot, now);
           waited = now - it.issued_ms;
         }
-        const uint8_t* base = ring_ + (int64_t)it.pslot * ring_stride_;
-        ColpackPiece pp;
-        if (it.packed) {  // a header that fails its checks fails the step and is never unpacked
-          const char* why = "";
-          if (!colpack_open(base, it.copied, kTeraRecordBytes, it.bytes / kTeraRecordBytes, &pp, &why) || !pp.packed)
-            throw std::runtime_error(std::string("packed piece rejected: ") + (pp.hdr ? "not marked packed" : why));
-        }
-        if (check && !it.packed)
-          for (int64_t off = 0; off + kTeraRecordBytes <= it.bytes; off += kTeraRecordBytes)
-            got_ck += record_hash(base + off, kTeraRecordBytes);
-        for (int64_t off = 0; off < it.bytes; off += buf_bytes) {
-          const int64_t len = std::min(buf_bytes, it.bytes - off);
-          const bool final_chunk = it.last && off + len >= it.bytes;
-          if (it.packed) {  // unpack this buffer's rows into a staging buffer; the sink gets that
-            uint8_t* stg = unpack_bufs_[i].get() + (size_t)(unpack_turn++ & 1) * unpack_one;
-            if (check || (sink_ && !err)) {  // no sink: nothing is unpacked
-              const double tu = now_ms();
-              colpack_unpack(pp, off / kTeraRecordBytes, len / kTeraRecordBytes, stg);
-              unpack_ms += now_ms() - tu;
-            }
-            if (check)
-              for (int64_t o = 0; o + kTeraRecordBytes <= len; o += kTeraRecordBytes)
-                got_ck += record_hash(stg + o, kTeraRecordBytes);
-            if (final_chunk && len + kEofBytes <= cfg_.kv_buf_bytes) {
-              stg[len] = 0xFF;
-              stg[len + 1] = 0xFF;
-              if (sink_ && !err) err = sink_(i, stg, len + kEofBytes);
-              eof_sent = true;
-            } else if (sink_ && !err) {
-              err = sink_(i, stg, len);
-            }
-            ++nb;
-            continue;
-          }
-          if (final_chunk && len + kEofBytes <= cfg_.kv_buf_bytes) {
-            std::memcpy(eb, base + off, (size_t)len);
-            eb[len] = 0xFF;
-            eb[len + 1] = 0xFF;
-            if (sink_ && !err) err = sink_(i, eb, len + kEofBytes);
-            eof_sent = true;
-          } else if (sink_ && !err) {
-            err = sink_(i, base + off, len);
-          }
-          ++nb;
-        }
+        p.base = lay_.slot(ring_, it.pslot);
+        p.copied = it.copied;
+        p.record_bytes = it.bytes;
+        p.packed = it.packed;
       }
-      if (it.last && !eof_sent) {  // EOF did not fit (or no final data): a separate buffer
-        eb[0] = 0xFF;
-        eb[1] = 0xFF;
-        if (sink_ && !err) err = sink_(i, eb, kEofBytes);
-        ++nb;
-      }
+      // What the delivery hands its buffers to: the check_delivery checksum of their records (not of the
+      // EOF marker) and the job's sink. A sink error ends that sink's part in this item and fails the
+      // step in run_step; it never fails the delivery, whose threads go on to the next step. Neither a
+      // sink nor a checksum: an empty FixedSink, and a packed piece is checked but not unpacked.
+      uint64_t got_ck = 0;
+      int err = 0;
+      FixedSink take;
+      if (sink_ || check)
+        take = [&](const uint8_t* b, int64_t len) {
+          if (check)
+            for (int64_t o = 0; o + kTeraRecordBytes <= len; o += kTeraRecordBytes)
+              got_ck += record_hash(b + o, kTeraRecordBytes);
+          if (sink_ && !err) err = sink_(i, b, len);
+          return 0;
+        };
+      FixedDeliveryCounters c;
+      deliver_fixed_piece(p, lay_.buf_bytes, lay_.kv_buf_bytes, bufs, take, &c);
       {
         std::lock_guard<std::mutex> g(mu_);
         if (it.pslot >= 0) pinned_free_[it.pslot] = true;
         if (check && it.q >= 0 && it.q < Q_) delivered_ck_[(size_t)it.q * R_ + i] += got_ck;
-        step_buffers_ += nb;
+        step_buffers_ += c.buffers;
         step_d2h_ms_ += waited;
-        step_unpack_ms_ += unpack_ms;
+        step_unpack_ms_ += c.unpack_ms;
         if (err && !step_error_) step_error_ = err;
         if (it.last && ++eof_count_ == R_) eof_done_ms_ = now_ms();
       }
@@ -2242,8 +2197,8 @@ StepStats ShuffleJob::run_step(bool validate) {
       // pieces [a, b) of the round's issue-ordered descriptors: pack them, results to the pinned table
       auto pack_range = [&](int a, int b) {
         launch_colpack(d_pack_pieces_[q].as<ColpackPieceDesc>() + a, b - a, pack_max_nrec_[q], kTeraRecordBytes,
-                       buf_records_, d_pack_table_.as<uint32_t>(), d_pack_results_[slot].as<ColpackResult>() + a,
-                       s_compute_, pack_version_, kTeraKeyOffset, kTeraKeyBytes);
+                       lay_.buf_records, d_pack_table_.as<uint32_t>(), d_pack_results_[slot].as<ColpackResult>() + a,
+                       s_compute_, lay_.pack_version, kTeraKeyOffset, kTeraKeyBytes);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpyAsync(h_pack_results_[slot].as<ColpackResult>() + a,
                                  d_pack_results_[slot].as<ColpackResult>() + a, (size_t)(b - a) * sizeof(ColpackResult),

@@ -40,6 +40,7 @@
 
 #include "delivery_schedule.h"
 #include "exchange.h"
+#include "fixed_delivery.h"
 #include "kernels.h"
 #include "disk_store.h"
 #include "sdma.h"
@@ -487,8 +488,9 @@ class ShuffleJob {
   int h2d_blocks_ = 2048;  // workgroups per descriptor (UDA_H2D_BLOCKS)
   bool sdma_h2d_ = true;   // pinned-DRAM tier, W == 1: stage on an SDMA engine (UDA_H2D_SDMA)
   hipStream_t s_stage_ = nullptr;  // disk tier, W == 1: H2D of the staging thread
-  int64_t buf_records_ = 0;
-  int64_t piece_bytes_ = 0;
+  // delivery geometry (fixed_delivery.h): records per buffer, the D2H piece, the pinned ring's slots
+  // and, packed, a piece's bound; pack_version 0 when the pieces travel as they are
+  FixedLayout lay_;
   // delivery bit-packing (cfg.delivery_pack): after a round's merge its output slot is packed piece by
   // piece into the packed slot of the same parity; every piece has a fixed region there (its bound),
   // and the per-piece lengths and flags reach the copy thread through a pinned table per slot
@@ -500,9 +502,7 @@ class ShuffleJob {
   // the D2H pieces of a round, reducer-major: delivery_schedule()'s pack_index numbers them (reducers with
   // no records this round have none)
   std::vector<PackPiece> round_pieces(const std::vector<int64_t>& group_recs) const;
-  int64_t pack_bound(int64_t nrec) const;      // a piece's region in the packed slot and the ring
   bool pack_ = false;
-  int pack_version_ = 2;                       // colpack format version of the packed pieces
   std::vector<DeviceBuffer> packed_slots_;     // per slot
   std::vector<DeviceBuffer> d_pack_pieces_;    // per round: ColpackPieceDesc[pack_n_[q]], in issue order
   std::vector<int> pack_n_;
@@ -516,13 +516,12 @@ class ShuffleJob {
   // per slot, a round's results in issue order: the first pack_early_[q] valid once early_ev_[slot] has
   // passed, all of them once merged_ev_[slot] has
   std::vector<PinnedBuffer> h_pack_results_;
-  int64_t ring_stride_ = 0;                    // bytes per pinned ring slot (>= piece_bytes_)
   double last_d2h_ratio_ = -1;                 // last step: d2h_bytes / bytes_in
   int last_delta_ = -1;                        // last step: 1 when every packed piece was delta, -1: no step yet
 
   // ---- delivery: copy thread -> pinned ring (SDMA) -> per-reducer consumer threads
   std::unique_ptr<SdmaEngine> sdma_;
-  uint8_t* ring_ = nullptr;          // pinned_slots x piece_bytes_
+  uint8_t* ring_ = nullptr;          // lay_.slots x lay_.slot_bytes
   std::string ring_numa_;            // where the ring's pages live (/proc/self/numa_maps)
   std::vector<hsa_signal_t> piece_sig_;
   std::vector<hipEvent_t> piece_ev_;
@@ -568,8 +567,9 @@ class ShuffleJob {
   void note_landing(int k, double now);    // mu_ held
   void poll_landings();                    // mu_ held: pieces whose copy is done but nobody has waited for yet
   SinkFn sink_;
-  std::vector<std::unique_ptr<uint8_t[]>> eof_bufs_;  // per reducer: final chunk + EOF marker
-  std::vector<std::unique_ptr<uint8_t[]>> unpack_bufs_;  // per reducer: two staging buffers, alternating
+  // per reducer, deliver_fixed_piece's FixedBuffers: the tail buffer and, packed, the two staging buffers
+  std::vector<std::unique_ptr<uint8_t[]>> eof_bufs_;
+  std::vector<std::unique_ptr<uint8_t[]>> unpack_bufs_;
 };
 
 // ncclUniqueId as bytes (rank 0 creates, others receive it out of band).

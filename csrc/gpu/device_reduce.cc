@@ -30,6 +30,10 @@
 namespace uda {
 namespace gpu {
 
+// fixed_delivery.h cannot include kernels.h (no HIP there): its copies of the record geometry
+static_assert(kFixedRecordBytes == kTeraRecordBytes, "fixed_delivery.h and kernels.h disagree on the record");
+static_assert(kFixedEofBytes == kEofBytes, "fixed_delivery.h and uda/vint.h disagree on the EOF marker");
+
 namespace {
 double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -328,10 +332,7 @@ class FixedDelivery {
         }
         const ColpackResult pr = host_results()[at];
         if (pr.packed) {
-          if (pr.bytes < (int64_t)kColpackHeaderBytes || pr.bytes > lay_.piece_bound(len / kTeraRecordBytes) ||
-              pr.bytes > lay_.slot_bytes)
-            throw std::runtime_error("device reduce: packed length outside the piece's region");
-          h = Held{pr.bytes, true};
+          h = Held{lay_.packed_copy_len(pr.bytes, len / kTeraRecordBytes), true};
           from = ws_.pring.as<uint8_t>() + (int64_t)at * lay_.region_bytes;
           st_.delta_pieces += pr.delta ? 1 : 0;
         }

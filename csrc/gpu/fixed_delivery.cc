@@ -39,6 +39,12 @@ int64_t FixedLayout::piece_bound(int64_t nrec) const {
                                               : colpack2_bound(kFixedRecordBytes, nrec, buf_records);
 }
 
+int64_t FixedLayout::packed_copy_len(int64_t packed_bytes, int64_t nrec) const {
+  if (packed_bytes < (int64_t)kColpackHeaderBytes || packed_bytes > piece_bound(nrec) || packed_bytes > slot_bytes)
+    throw std::runtime_error("fixed delivery: packed length outside the piece's region");
+  return packed_bytes;
+}
+
 FixedLayout fixed_layout(int64_t kv_buf_bytes, int64_t piece_bytes, int pinned_slots, int pack_version) {
   FixedLayout l;
   l.pack_version = pack_version;
@@ -73,17 +79,21 @@ void deliver_fixed_piece(const FixedPiece& p, int64_t buf_bytes, int64_t kv_buf_
   } else if (p.copied != p.record_bytes) {
     throw std::runtime_error("fixed delivery: an unpacked piece of another length than its records");
   }
+  const bool drop = !sink;  // no sink: the buffers are counted, none is built
   auto emit = [&](const uint8_t* b, int64_t len) {
-    const double a = now_ms();
-    if (sink(b, len) != 0) throw std::runtime_error("dataFromUda callback failed");
-    c->sink_ms += now_ms() - a;
+    if (!drop) {
+      const double a = now_ms();
+      if (sink(b, len) != 0) throw std::runtime_error("dataFromUda callback failed");
+      c->sink_ms += now_ms() - a;
+    }
     c->buffers++;
   };
   for (int64_t off = 0; off < p.record_bytes; off += buf_bytes) {
     const int64_t len = std::min(buf_bytes, p.record_bytes - off);
     const bool eof_here = p.last && off + len >= p.record_bytes && len + kFixedEofBytes <= kv_buf_bytes;
     const uint8_t* out = p.base + off;
-    if (p.packed) {  // this buffer's rows into a staging buffer; the sink gets that
+    if (drop) {
+    } else if (p.packed) {  // this buffer's rows into a staging buffer; the sink gets that
       uint8_t* stg = bufs.staging[bufs.turn++ & 1];
       const double a = now_ms();
       colpack_unpack(pp, off / kFixedRecordBytes, len / kFixedRecordBytes, stg);
@@ -99,7 +109,7 @@ void deliver_fixed_piece(const FixedPiece& p, int64_t buf_bytes, int64_t kv_buf_
     if (eof_here) c->eof_sent = true;
   }
   if (p.last && !c->eof_sent) {  // EOF did not fit (or no records): a buffer of its own
-    bufs.tail[0] = bufs.tail[1] = 0xFF;
+    if (!drop) bufs.tail[0] = bufs.tail[1] = 0xFF;
     emit(bufs.tail, kFixedEofBytes);
     c->eof_sent = true;
   }

@@ -1,5 +1,5 @@
-// Host side of the FIXED10 delivery (device_reduce.h): what happens to one D2H piece once it has landed
-// in the pinned ring. A piece stands for whole 104-byte records of one key-range round; it arrives either
+// Host side of the FIXED10 delivery, for the reduce tasks of the C ABI (device_reduce.h) and for ShuffleJob's
+// consumer threads (device_engine.h) alike: what happens to one D2H piece once it has landed in the pinned ring. A piece stands for whole 104-byte records of one key-range round; it arrives either
 // as those records or as a colpack piece (codec/colpack.h) that unpacks to them. Either way the sink gets
 // the same buffers: <= kv_buf whole records each, the task's last one carrying the IFile EOF marker when
 // it fits and a separate 2-byte buffer after it when it does not.
@@ -37,6 +37,10 @@ struct FixedLayout {
   size_t ring_bytes = 0;      // slots * slot_bytes (+ 2 * staging_bytes)
   // upper bound of a piece of nrec records in its packed form (version 1 or 2)
   int64_t piece_bound(int64_t nrec) const;
+  // The length to copy for a piece of nrec records that the device packed into `packed_bytes`
+  // (ColpackResult::bytes): that length, once it is known to hold a header and to fit the piece's bound
+  // and a ring slot. Throws std::runtime_error otherwise.
+  int64_t packed_copy_len(int64_t packed_bytes, int64_t nrec) const;
   uint8_t* slot(uint8_t* ring, int64_t k) const { return ring + (k % slots) * slot_bytes; }
   uint8_t* staging(uint8_t* ring, int i) const { return ring + (int64_t)slots * slot_bytes + (i & 1) * staging_bytes; }
 };
@@ -68,7 +72,8 @@ using FixedSink = std::function<int(const uint8_t*, int64_t)>;
 // Hand the piece's records to the sink in buffers of buf_bytes (the last may be short). A packed piece's
 // header is checked first (colpack_open against record_bytes / 104 records): one that fails a check, or
 // is not marked packed, throws std::runtime_error before the sink is called and is never unpacked. A
-// nonzero sink return throws as well.
+// nonzero sink return throws as well. An empty sink drops the piece: its header is checked and its
+// buffers and EOF are counted as with a sink, but nothing is unpacked, copied or written to `bufs`.
 void deliver_fixed_piece(const FixedPiece& p, int64_t buf_bytes, int64_t kv_buf_bytes, FixedBuffers& bufs,
                          const FixedSink& sink, FixedDeliveryCounters* c);
 

@@ -482,9 +482,10 @@ PYBIND11_MODULE(_uda_native, m) {
   }, py::arg("pieces"), py::arg("record_bytes"), py::arg("buf_records"), py::arg("key_off"), py::arg("key_len"),
      py::arg("device") = 0);
   // FIXED10 delivery (gpu/fixed_delivery.h, gpu/device_reduce.h)
-  // The buffers the host side of the delivery hands the sink for one landed piece. No GPU.
+  // The buffers the host side of the delivery hands the sink for one landed piece. No GPU. deliver=False:
+  // an empty sink; returns the counters (buffers, eof_sent, unpack_ms) instead.
   m.def("fixed_delivery_piece", [](py::bytes piece, int64_t record_bytes, int64_t buf_bytes, int64_t kv_buf, bool packed,
-                                   bool last) {
+                                   bool last, bool deliver) -> py::object {
     std::string s = piece;
     if (kv_buf < 1 || buf_bytes < 1) throw py::value_error("fixed_delivery_piece: bad buffer sizes");
     const size_t one = (size_t)std::max(kv_buf, buf_bytes) + 16;
@@ -501,15 +502,31 @@ PYBIND11_MODULE(_uda_native, m) {
     p.last = last;
     std::vector<std::string> out;
     gpu::FixedDeliveryCounters c;
-    gpu::deliver_fixed_piece(p, buf_bytes, kv_buf, bufs, [&](const uint8_t* b, int64_t len) {
-      out.emplace_back((const char*)b, (size_t)len);
-      return 0;
-    }, &c);
+    gpu::FixedSink sink;
+    if (deliver)
+      sink = [&](const uint8_t* b, int64_t len) {
+        out.emplace_back((const char*)b, (size_t)len);
+        return 0;
+      };
+    gpu::deliver_fixed_piece(p, buf_bytes, kv_buf, bufs, sink, &c);
+    if (!deliver) {
+      py::dict d;
+      d["buffers"] = c.buffers;
+      d["eof_sent"] = c.eof_sent;
+      d["unpack_ms"] = c.unpack_ms;
+      return d;
+    }
     py::list ret;
     for (const auto& b : out) ret.append(py::bytes(b));
     return ret;
-  }, py::arg("piece"), py::arg("record_bytes"), py::arg("buf_bytes"), py::arg("kv_buf"), py::arg("packed"), py::arg("last"));
+  }, py::arg("piece"), py::arg("record_bytes"), py::arg("buf_bytes"), py::arg("kv_buf"), py::arg("packed"), py::arg("last"),
+     py::arg("deliver") = true);
   m.def("delivery_pack_version", &gpu::delivery_pack_version);
+  // FixedLayout::packed_copy_len of the layout fixed_delivery_layout describes
+  m.def("fixed_delivery_packed_copy_len", [](int64_t kv_buf, int64_t piece_bytes, int pinned_slots, int pack_version,
+                                             int64_t packed_bytes, int64_t nrec) {
+    return gpu::fixed_layout(kv_buf, piece_bytes, pinned_slots, pack_version).packed_copy_len(packed_bytes, nrec);
+  });
   m.def("fixed_delivery_layout", [](int64_t kv_buf, int64_t piece_bytes, int pinned_slots, int pack_version) {
     const gpu::FixedLayout l = gpu::fixed_layout(kv_buf, piece_bytes, pinned_slots, pack_version);
     py::dict d;

@@ -1,7 +1,8 @@
 // Stand-alone check of the FIXED10 piece delivery in csrc/gpu/fixed_delivery.cc, meant to be built with
 // -fsanitize=address,undefined together with csrc/codec/colpack.cc: pieces, staging buffers and the tail
 // buffer are exact-size heap allocations, so a read past a piece or a write past kv_buf + 16 is
-// reported. Every delivery is compared with plain slicing of the records plus the EOF rule.
+// reported. Every delivery is compared with plain slicing of the records plus the EOF rule, and repeated
+// with an empty sink over staging and tail buffers of one byte: it counts the same buffers and writes nothing.
 // Prints "<n> checks, <m> failures".
 #include "fixed_delivery.h"
 
@@ -73,13 +74,15 @@ struct Run {
   std::string what;
 };
 
-// piece: exactly `len` heap bytes; staging and tail exactly as large as the header says they must be
+// piece: exactly `len` heap bytes; staging and tail exactly as large as the header says they must be.
+// drop: an empty sink, and staging and tail of one byte each (nothing may be written to them)
 static Run deliver(const uint8_t* piece, int64_t len, int64_t record_bytes, int64_t buf_bytes, int64_t kv_buf, bool packed,
-                   bool last) {
+                   bool last, bool drop = false) {
   Run r;
   auto p = exact(piece, (size_t)len);
-  const size_t one = (size_t)std::max(kv_buf, buf_bytes) + 16;
-  std::unique_ptr<uint8_t[]> s0(new uint8_t[one]), s1(new uint8_t[one]), tail(new uint8_t[(size_t)kv_buf + 16]);
+  const size_t one = drop ? 1 : (size_t)std::max(kv_buf, buf_bytes) + 16;
+  std::unique_ptr<uint8_t[]> s0(new uint8_t[one]), s1(new uint8_t[one]), tail(new uint8_t[drop ? 1 : (size_t)kv_buf + 16]);
+  s0[0] = s1[0] = tail[0] = 0x5C;
   FixedBuffers b;
   b.staging[0] = s0.get();
   b.staging[1] = s1.get();
@@ -90,15 +93,19 @@ static Run deliver(const uint8_t* piece, int64_t len, int64_t record_bytes, int6
   fp.record_bytes = record_bytes;
   fp.packed = packed;
   fp.last = last;
-  try {
-    deliver_fixed_piece(fp, buf_bytes, kv_buf, b, [&](const uint8_t* d, int64_t n) {
+  FixedSink sink;
+  if (!drop)
+    sink = [&](const uint8_t* d, int64_t n) {
       r.bufs.emplace_back((const char*)d, (size_t)n);
       return 0;
-    }, &r.c);
+    };
+  try {
+    deliver_fixed_piece(fp, buf_bytes, kv_buf, b, sink, &r.c);
   } catch (const std::runtime_error& e) {
     r.threw = true;
     r.what = e.what();
   }
+  if (drop) CHECK(s0[0] == 0x5C && s1[0] == 0x5C && tail[0] == 0x5C && r.c.unpack_ms == 0);
   return r;
 }
 
@@ -125,12 +132,28 @@ static void both_ways(const std::vector<uint8_t>& raw, int64_t buf_records, int6
   Run b = deliver(raw.data(), (int64_t)raw.size(), (int64_t)raw.size(), buf_bytes, kv_buf, false, last);
   CHECK(!b.threw && b.bufs == want);
   CHECK(b.c.buffers == (int64_t)want.size() && b.c.eof_sent == last);
+  // no sink: the same count, nothing built
+  Run c = deliver(piece.data(), (int64_t)piece.size(), (int64_t)raw.size(), buf_bytes, kv_buf, true, last, true);
+  CHECK(!c.threw && c.c.buffers == a.c.buffers && c.c.eof_sent == a.c.eof_sent);
+  Run d = deliver(raw.data(), (int64_t)raw.size(), (int64_t)raw.size(), buf_bytes, kv_buf, false, last, true);
+  CHECK(!d.threw && d.c.buffers == b.c.buffers && d.c.eof_sent == b.c.eof_sent);
 }
 
 static void rejected(const std::vector<uint8_t>& piece, int64_t record_bytes, bool packed, const char* reason) {
   Run r = deliver(piece.data(), (int64_t)piece.size(), record_bytes, 78 * L, 8192, packed, true);
   CHECK(r.threw && r.bufs.empty());
   CHECK(r.what.find(reason) != std::string::npos);
+  Run e = deliver(piece.data(), (int64_t)piece.size(), record_bytes, 78 * L, 8192, packed, true, true);  // no sink
+  CHECK(e.threw && e.c.buffers == 0 && e.what == r.what);
+}
+
+static bool copy_len_throws(const FixedLayout& l, int64_t bytes, int64_t nrec) {
+  try {
+    CHECK(l.packed_copy_len(bytes, nrec) == bytes);
+    return false;
+  } catch (const std::runtime_error&) {
+    return true;
+  }
 }
 
 int main() {
@@ -150,6 +173,8 @@ int main() {
   {
     Run r = deliver(nullptr, 0, 0, 78 * L, 8192, false, true);  // the marker alone
     CHECK(!r.threw && r.bufs.size() == 1 && r.bufs[0] == "\xff\xff");
+    Run e = deliver(nullptr, 0, 0, 78 * L, 8192, false, true, true);
+    CHECK(!e.threw && e.c.buffers == 1 && e.c.eof_sent);
   }
   {
     // values of any byte: the encoder says raw, the records travel as they are
@@ -176,6 +201,18 @@ int main() {
     rejected(std::vector<uint8_t>(piece.begin(), piece.end() - 64), (int64_t)raw.size(), true, "exceed the piece's length");
     rejected(std::vector<uint8_t>(piece.begin(), piece.begin() + 100), (int64_t)raw.size(), true, "shorter than its header");
     rejected(std::vector<uint8_t>(raw.begin(), raw.end() - L), (int64_t)raw.size(), false, "another length");
+  }
+  // a packed length from the device: a header at least, the piece's bound and a ring slot at most
+  {
+    const FixedLayout l = fixed_layout(8192, 32 << 10, 4, 2);
+    const int64_t bound = l.piece_bound(312);
+    CHECK(l.piece_recs == 312 && bound <= l.slot_bytes);
+    CHECK(!copy_len_throws(l, (int64_t)kColpackHeaderBytes, 312) && !copy_len_throws(l, bound, 312));
+    CHECK(copy_len_throws(l, (int64_t)kColpackHeaderBytes - 1, 312) && copy_len_throws(l, bound + 1, 312));
+    CHECK(copy_len_throws(l, l.piece_bound(1) + 1, 1));  // the bound of this piece, not of a full one
+    const FixedLayout tiny = fixed_layout(104, 104, 2, 2);
+    CHECK(tiny.slot_bytes == 832 && !copy_len_throws(tiny, 832, 1) && copy_len_throws(tiny, 833, 1));
+    CHECK(copy_len_throws(tiny, 896, 400));  // within the bound of 400 records, past the slot
   }
   // sweep: every piece size against three buffer sizes, as the task's last piece and not
   for (int64_t buf_records : {1, 13, 78})

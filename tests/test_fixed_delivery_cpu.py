@@ -2,7 +2,8 @@
 (colpack version 2) or as records, becomes the buffers the sink gets. Every case is compared with plain
 slicing of the records into buf_bytes chunks plus the EOF rule: the marker rides in the task's last
 buffer when it fits kv_buf and follows in a 2-byte buffer of its own when it does not. A packed piece
-whose header fails a check raises and delivers nothing. Also the stand-alone selftest under ASan + UBSan."""
+whose header fails a check raises and delivers nothing; with an empty sink the piece is checked and its
+buffers counted, nothing else. Also the stand-alone selftest under ASan + UBSan."""
 import os
 import shutil
 import struct
@@ -120,6 +121,52 @@ def test_rejected_pieces_raise_and_deliver_nothing(native):
         native.fixed_delivery_piece(header_only, *args)
     with pytest.raises(RuntimeError, match="another length"):  # an unpacked piece must be its records
         native.fixed_delivery_piece(raw[:-L], len(raw), 78 * L, 8192, False, True)
+
+
+@pytest.mark.parametrize("packed", [True, False])
+@pytest.mark.parametrize("name", list(SHAPES))
+def test_empty_sink_counts_the_same_buffers(native, name, packed):
+    """No sink (the flagship's --sink none): the piece is checked and counted, nothing is unpacked."""
+    n, buf_records, kv_buf, last = SHAPES[name]
+    raw = _raw(n)
+    piece = packed_piece(native, raw, buf_records) if packed else raw
+    args = (piece, len(raw), buf_records * L, kv_buf, packed, last)
+    with_sink = native.fixed_delivery_piece(*args)
+    c = native.fixed_delivery_piece(*args, deliver=False)
+    assert c["buffers"] == len(with_sink) == len(expected(raw, buf_records * L, kv_buf, last))
+    assert c["eof_sent"] == last == (bool(with_sink) and with_sink[-1].endswith(EOF))
+    assert c["unpack_ms"] == 0
+
+
+def test_empty_sink_still_rejects_a_bad_header(native):
+    raw = _raw(312)
+    piece = packed_piece(native, raw, 78)
+    args = (len(raw), 78 * L, 8192, True, True)
+    assert native.fixed_delivery_piece(piece, *args, deliver=False)["buffers"] == 4
+    magic = struct.unpack_from("<I", piece, 0)[0]
+    with pytest.raises(RuntimeError, match="bad magic"):
+        native.fixed_delivery_piece(_patched(piece, 0, "<I", magic ^ 0x100), *args, deliver=False)
+    with pytest.raises(RuntimeError, match="record count"):
+        native.fixed_delivery_piece(piece, 311 * L, 78 * L, 8192, True, True, deliver=False)
+    with pytest.raises(RuntimeError, match="another length"):
+        native.fixed_delivery_piece(raw[:-L], len(raw), 78 * L, 8192, False, True, deliver=False)
+
+
+def test_packed_copy_len_accepts_header_to_bound(native):
+    """The one check of a packed length the device reported, before it becomes a copy length: at least
+    a header, at most the piece's bound, at most a ring slot."""
+    lay = (8192, 32 << 10, 4, 2)
+    bound = native.fixed_delivery_layout(*lay)["bound_full"]  # a piece of 312 records
+    assert bound > HEADER_BYTES
+    for ok in (HEADER_BYTES, bound):
+        assert native.fixed_delivery_packed_copy_len(*lay, ok, 312) == ok
+    for bad in (HEADER_BYTES - 1, bound + 1):
+        with pytest.raises(RuntimeError, match="packed length"):
+            native.fixed_delivery_packed_copy_len(*lay, bad, 312)
+    tiny = (104, 104, 2, 2)  # bound and slot 832
+    assert native.fixed_delivery_packed_copy_len(*tiny, 832, 1) == 832
+    with pytest.raises(RuntimeError, match="packed length"):
+        native.fixed_delivery_packed_copy_len(*tiny, 833, 1)
 
 
 def test_pack_key_values(native, monkeypatch):
