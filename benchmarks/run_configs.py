@@ -14,6 +14,8 @@
   aio                 AsyncIO (io_uring / thread pool, O_DIRECT) read bandwidth vs sequential pread.
   spill               TeraSort whose map outputs live in pinned host DRAM (the spill tier used when a
                       job exceeds HBM): rounds are streamed H2D, merged on the GPU, delivered D2H.
+  combine             wordcount over HBM-resident MOFs, 16 concurrent reduce tasks, 16 and 64 maps:
+                      mapred.uda.merge.combine none vs sum.int, and the F4 kernels phase by phase.
 
 Each prints one JSON line per result. Data is synthetic (native generators, csrc/engine/datagen.cc).
 """
@@ -455,10 +457,103 @@ def radix(args) -> dict:
             "hbm_gbps_est": round(moved / ms / 1e6, 1), "matches_numpy_lexsort": bool(ok)}
 
 
+def _combine_tasks(n, maps: int, tasks: int, rows: int, op: str, steps: int, warmup: int) -> dict:
+    """`tasks` concurrent reduce tasks over HBM-resident wordcount MOFs, `warmup` + `steps` times."""
+    from uda_amd.bridge import UdaConsumer, UdaProvider
+    from uda_amd.utils.datagen import TEXT
+    from uda_amd.utils.mof import encode_partitions
+    runs = n.generate_runs("wordcount", maps, tasks, rows, 7)
+    prov = UdaProvider()
+    total = 0
+    for m, parts in enumerate(runs):
+        data, index = encode_partitions(parts)
+        total += len(data) - 2 * len(parts)
+        prov.add_mof_device("job_cb", f"attempt_cb_m_{m:06d}_0", data, index)
+    del runs
+    conf = {"mapred.uda.merge.backend": "gpu", "mapred.uda.gpu.fetch": "device", "mapred.uda.merge.combine": op}
+    gbps, last = [], None
+    for step in range(warmup + steps):
+        cons = [UdaConsumer(maps, "job_cb", f"attempt_cb_r_{r:06d}_{step}", TEXT, conf=conf, keep_records=False)
+                for r in range(tasks)]
+        t0 = time.perf_counter()
+        for m in range(maps):
+            for r, c in enumerate(cons):
+                c.fetch("localhost", "job_cb", f"attempt_cb_m_{m:06d}_0", r)
+        for c in cons:
+            c.wait(3600)
+        wall = time.perf_counter() - t0
+        last = [c.close() for c in cons]
+        if step >= warmup:
+            gbps.append(total / wall / 1e9)
+    prov.close()
+    mean = lambda k: round(sum(st[k] for st in last) / len(last), 2)  # noqa: E731
+    return {"input_gb": round(total / 1e9, 3), "input_gbps": [round(x, 2) for x in sorted(gbps)],
+            "input_gbps_min_med_max": [round(min(gbps), 2), round(sorted(gbps)[len(gbps) // 2], 2), round(max(gbps), 2)],
+            "bytes_delivered": sum(st["bytes_delivered"] for st in last), "records": sum(st["records"] for st in last),
+            "combine": sorted({st.get("combine", "none") for st in last}),
+            "merge_path": sorted({st["merge_path"] for st in last}),
+            "combine_in_records": sum(st.get("combine_in_records", 0) for st in last),
+            "combine_groups": sum(st.get("combine_groups", 0) for st in last),
+            "task_mean_ms": {k: mean(k) for k in ("gpu_device_ms", "gpu_d2h_wait_ms", "gpu_sink_ms", "merge_ms")}}
+
+
+def combine_kernels(args) -> dict:
+    """One task's runs through ops.merge_runs with UDA_GM_PROFILE set by the caller: prints the merger's
+    phase lines on stderr (the whole path: every F4 kernel is a phase of its own)."""
+    from uda_amd import native, ops
+    from uda_amd.utils.datagen import TEXT
+    rows = int(args.gb * 1e9 / args.maps / 17)
+    runs = [p[0] for p in native().generate_runs("wordcount", args.maps, args.reducers, rows, 7)]
+    out = {}
+    for op in ("none", "sum.int"):
+        for _ in range(3):
+            body, _ = ops.merge_runs(runs, TEXT, "gpu", combine=op)
+        out[op] = {"records_in": ops.last_stats["records_in"], "records": ops.last_stats["records"], "bytes": len(body)}
+    return out
+
+
+def combine(args) -> dict:
+    """Reduce-side combiner (mapred.uda.merge.combine) on a wordcount-shaped job: 16 concurrent reduce
+    tasks over HBM-resident MOFs of 16 and of 64 maps, `none` against `sum.int`, five steps each after two
+    warm-ups; then the F4 kernels of one task's merge, phase by phase, from a child process under
+    UDA_GM_PROFILE (each phase is synchronized: kernel time plus one launch and sync)."""
+    import re
+    import subprocess
+    from uda_amd import native
+    n = native()
+    out = {"config": "wordcount, 16 reduce tasks over HBM-resident MOFs, combine none vs sum.int", "tasks": 16}
+    for maps in (16, 64):
+        rows = int(args.gb * 1e9 / maps / 17)
+        for op in ("none", "sum.int"):
+            r = _combine_tasks(n, maps, 16, rows, op, steps=5, warmup=2)
+            print(f"# maps={maps} {op}: {json.dumps(r)}", file=sys.stderr, flush=True)
+            out[f"maps{maps}_{op}"] = r
+        a, b = out[f"maps{maps}_none"], out[f"maps{maps}_sum.int"]
+        out[f"maps{maps}_records_per_group"] = round(b["combine_in_records"] / max(1, b["combine_groups"]), 1)
+        out[f"maps{maps}_delivered_ratio"] = round(a["bytes_delivered"] / max(1, b["bytes_delivered"]), 1)
+        # kernel phases of one task's merge (last of three calls per op)
+        env = dict(os.environ, UDA_GM_PROFILE="1")
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "combine_kernels", "--gb", str(args.gb),
+                            "--maps", str(maps), "--reducers", "16"], env=env, capture_output=True, text=True,
+                           timeout=600)
+        lines = [ln for ln in p.stderr.splitlines() if ln.startswith("[GM profile]")]
+        if p.returncode != 0 or len(lines) != 6:
+            raise RuntimeError("combine_kernels failed: " + p.stderr[-2000:])
+        ph = {}
+        for op, ln in (("none", lines[2]), ("sum.int", lines[5])):
+            ph[op] = {k: float(v) for k, v in re.findall(r"(f[34]c?_\w+)=([0-9.]+)ms", ln)}
+        out[f"maps{maps}_kernel_phases_ms"] = ph
+        base = sum(ph["none"].get(k, 0) for k in ("f4_record_sizes", "f4_scan", "f4_gather_var"))
+        new = sum(ph["sum.int"].get(k, 0) for k in ("f4c_heads", "f4c_group_scan", "f4c_sums"))
+        out[f"maps{maps}_heads_plus_sums_over_plain_f4"] = round(new / base, 2) if base else None
+        out[f"maps{maps}_one_task"] = json.loads(p.stdout.strip().splitlines()[-1])
+    return out
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("config", choices=["wordcount_loopback", "wordcount_tcp", "cpu_reference", "secondary_sort", "spill", "decode", "aio",
-                                       "netmerger", "radix", "hybrid_budget"])
+                                       "netmerger", "radix", "hybrid_budget", "combine", "combine_kernels"])
     ap.add_argument("--dir", default="/tmp")
     ap.add_argument("--codec", default="snappy", choices=["snappy", "lzo", "lz4"])
     ap.add_argument("--gb", type=float, default=1.0)

@@ -69,6 +69,7 @@ struct DeviceMergeOut {
   int64_t bytes = 0;           // merged records (no EOF), resident in the workspace's `out`
   std::vector<int64_t> cuts;   // whole-record boundaries, <= the requested spacing apart
   int64_t records = 0;
+  int64_t records_in = 0;      // records merged (== records without a combiner)
   int64_t decoded_blocks = 0;
 };
 
@@ -592,7 +593,7 @@ struct GateLease {
 // delivery engine) instead of a blit kernel whose host reads would slow the merge kernels beside it.
 DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_runs, Codec codec, KeyKind kind,
                             int64_t spacing, hipStream_t s, const gpu::GenericMerger::RoundFn& on_round = nullptr,
-                            bool pinned_src = false) {
+                            bool pinned_src = false, CombineOp combine = CombineOp::kNone) {
   double round_ms = 0;
   gpu::GenericMerger::RoundFn timed;
   if (on_round)
@@ -621,13 +622,14 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
     auto t1 = std::chrono::steady_clock::now();
     ws.h2d_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
     gpu::GenericMergeResult r =
-        ws.merger.merge(runs, lens, (int)kind, ws.out.as<uint8_t>(), total, spacing, s, timed);
+        ws.merger.merge(runs, lens, (int)kind, ws.out.as<uint8_t>(), total, spacing, s, timed, 256ll << 20, combine);
     HIP_CHECK(hipStreamSynchronize(s));
     ws.device_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count() - round_ms;
     DeviceMergeOut res;
     res.bytes = r.bytes;
     res.cuts = std::move(r.cuts);
     res.records = r.records;
+    res.records_in = r.records_in;
     return res;
   }
   gpu::BlockPlan plan;
@@ -706,13 +708,15 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
     res.decoded_blocks = (int64_t)plan.descs.size();
   }
   host_raw.clear();
-  gpu::GenericMergeResult r = ws.merger.merge(runs, bytes, (int)kind, out.as<uint8_t>(), total, spacing, s, timed);
+  gpu::GenericMergeResult r =
+      ws.merger.merge(runs, bytes, (int)kind, out.as<uint8_t>(), total, spacing, s, timed, 256ll << 20, combine);
   HIP_CHECK(hipStreamSynchronize(s));
   ws.device_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count() - round_ms;
   if (tm) trace::host_event("dm_merge", total, (int64_t)ptrs.size(), tm, trace::now_ns());
   res.bytes = r.bytes;
   res.cuts = std::move(r.cuts);
   res.records = r.records;
+  res.records_in = r.records_in;
   return res;
 }
 
@@ -1870,7 +1874,12 @@ void ReduceTask::merge_gpu() {
 
     lpq_wait();  // an LPQ of the fetch phase may still be merging
     double prog_fetch_ms = -1;
+    // mapred.uda.merge.combine: the online and progressive merges combine; the over-budget hybrid (LPQ /
+    // RPQ rounds, progressive direct) delivers the uncombined stream, which a combiner allows
+    int64_t combine_in = 0;
+    bool combine_skipped = false;
     if (dprog) {
+      combine_skipped = combine_ != CombineOp::kNone;
       DirectProg& dp = *dprog;
       const int K = dp.K;
       // merge-owned views of the runs: the landed, indexed prefix of every partition
@@ -2109,13 +2118,16 @@ void ReduceTask::merge_gpu() {
             spans[(size_t)k] = Span{pf.dst[(size_t)k] + start[(size_t)k], pf.cap[(size_t)k] - start[(size_t)k],
                                     pf.dev[(size_t)k] + start[(size_t)k]};
         }
-        device_merge(ws, spans, Codec::kNone, kind_, kv, s,
-                     [&](const std::vector<int64_t>& cuts, int64_t records, bool last) {
-                       DeviceMergeOut r;
-                       r.cuts = cuts;
-                       r.records = records;
-                       deliver(r, last && last_phase, ws.copy_stream(), ws);
-                     });
+        const DeviceMergeOut pm =
+            device_merge(ws, spans, Codec::kNone, kind_, kv, s,
+                         [&](const std::vector<int64_t>& cuts, int64_t records, bool last) {
+                           DeviceMergeOut r;
+                           r.cuts = cuts;
+                           r.records = records;
+                           deliver(r, last && last_phase, ws.copy_stream(), ws);
+                         },
+                         false, combine_);
+        combine_in += pm.records_in;
       }
       for (auto& t : pf.threads) t.join();
       for (int k = 0; k < K; ++k) {
@@ -2144,10 +2156,13 @@ void ReduceTask::merge_gpu() {
                                         r.cuts = cuts;
                                         r.records = records;
                                         deliver(r, last, ws.copy_stream(), ws);
-                                      });
+                                      },
+                                      false, combine_);
+      combine_in += m.records_in;
       count_decoded(m.decoded_blocks);
     } else {
       // ---- hybrid: last LPQ, then RPQ rounds over the spilled runs (direct: over the partitions)
+      combine_skipped = combine_ != CombineOp::kNone;
       if (direct) {
         spills = direct_head.get();
         for (auto& r : direct_runs) spills.push_back(std::move(r));
@@ -2324,6 +2339,12 @@ void ReduceTask::merge_gpu() {
     stager_lease.clean = true;
     stager_lease2.clean = true;
     std::lock_guard<std::mutex> g(st_mu_);
+    if (combine_skipped) {
+      st_.combine = "skipped-over-budget";
+    } else if (combine_ != CombineOp::kNone) {
+      st_.combine_in_records = combine_in;
+      st_.combine_groups = st_.records;
+    }
     st_.gpu_h2d_ms = ws.h2d_ms + (ws2 ? ws2->h2d_ms : 0) + (ws3 ? ws3->h2d_ms : 0);
     st_.gpu_device_ms = ws.device_ms + (ws2 ? ws2->device_ms : 0) + (ws3 ? ws3->device_ms : 0);
     st_.gpu_d2h_wait_ms = ws.d2h_ms + (ws2 ? ws2->d2h_ms : 0) + (ws3 ? ws3->d2h_ms : 0);
@@ -2813,7 +2834,8 @@ bool ReduceTask::merge_gpu_device(bool probe) {
     // TeraSort-shaped partitions: decode per key-range round, only the blocks each round covers, so the
     // task's device memory is round-sized instead of its decoded partitions (DecompressorWrapper decodes
     // block by block next to the merge too, src/Merger/DecompressorWrapper.cc:85-114)
-    if (dev_frames && kind_ == KeyKind::kText && host_->conf_i64("mapred.uda.gpu.decode.stream", 1) != 0) {
+    if (dev_frames && kind_ == KeyKind::kText && combine_ == CombineOp::kNone &&
+        host_->conf_i64("mapred.uda.gpu.decode.stream", 1) != 0) {
       gpu::DeviceReduceConfig cfg;
       cfg.device = device;
       cfg.kv_buf_bytes = kv_buf_size_;
@@ -2914,7 +2936,7 @@ bool ReduceTask::merge_gpu_device(bool probe) {
     st_.gpu_decode_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
   }
   // ---- TeraSort-shaped input: FIXED10 rounds straight over the partitions
-  bool fixed = kind_ == KeyKind::kText;
+  bool fixed = kind_ == KeyKind::kText && combine_ == CombineOp::kNone;  // a combiner takes the generic merge
   std::vector<gpu::RunDesc> runs;
   for (const auto& p : parts) {
     const int64_t rec_bytes = p->part_len - kEofBytes;
@@ -2973,7 +2995,9 @@ bool ReduceTask::merge_gpu_device(bool probe) {
     const int64_t have = (int64_t)(ws.out.held() + ws.out2.held()) + ws.merger.workspace_bytes();
     admit(0, [&](int64_t rb) {
       const int64_t b = std::min(rb, total);
-      return std::max<int64_t>(0, (int64_t)(2.25 * (double)b + 1.4 * (double)b) - have);
+      // (a combiner's group index and sums: 17 B per record more, 0.27 of the bytes at 64 B records)
+      const double comb = combine_ != CombineOp::kNone ? 0.27 * (double)b : 0.0;
+      return std::max<int64_t>(0, (int64_t)(2.25 * (double)b + 1.4 * (double)b + comb) - have);
     });
   }
   if (total > round_bytes) {
@@ -3108,11 +3132,13 @@ bool ReduceTask::merge_gpu_device(bool probe) {
         [&](const std::vector<int64_t>& cuts, int64_t, bool last_inner) {
           push(DJob{dst, cuts, last_inner && last_outer, last_inner});
           round_closed = round_closed || last_inner;
-        });
+        },
+        256ll << 20, combine_);
     // slices holding only EOF markers: the merge saw no records and never called back, but the
     // delivery thread still has to count this round as handed over
     if (!round_closed) push(DJob{nullptr, {}, false, true});
     m.records += r.records;
+    m.records_in += r.records_in;
     if (trace::host_enabled())
       trace::host_event("gr_merge", (int64_t)(uintptr_t)&ws, q,
                         trace::now_ns() - (int64_t)(std::chrono::steady_clock::now() - tq).count(), trace::now_ns());
@@ -3143,6 +3169,10 @@ bool ReduceTask::merge_gpu_device(bool probe) {
   ws_lease.clean = true;
   std::lock_guard<std::mutex> g(st_mu_);
   st_.records = m.records;
+  if (combine_ != CombineOp::kNone) {
+    st_.combine_in_records = m.records_in;
+    st_.combine_groups = m.records;
+  }
   st_.fetch_ms = fetch_ms;
   st_.merge_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - fetch_ms;
   st_.merge_path = "device-generic";

@@ -448,6 +448,10 @@ void ReduceTask::on_init(const InitParams& p_in) {
     UDA_LOG(kInfo, "mapred.uda.merge.backend=auto: %s merge", backend_.c_str());
   }
   if (backend_ != "cpu" && backend_ != "gpu") throw ProtocolError("unknown mapred.uda.merge.backend " + backend_);
+  // reduce-side combiner (uda/combine.h): the job names its sum combiner itself
+  const std::string comb = host_->get_conf("mapred.uda.merge.combine", "none");
+  if (!combine_op_from_conf(comb, &combine_))
+    throw ProtocolError("unknown mapred.uda.merge.combine \"" + comb + "\" (" + kCombineAllowed + ")");
   if (backend_ == "gpu") {
     // FIXED10 delivery: bit-packed D2H pieces (gpu/fixed_delivery.h) and the D2H granule
     const std::string pack = host_->get_conf("mapred.uda.gpu.delivery.pack", "auto");
@@ -466,6 +470,7 @@ void ReduceTask::on_init(const InitParams& p_in) {
   {
     std::lock_guard<std::mutex> g(st_mu_);
     st_.backend = backend_;
+    st_.combine = combine_op_name(combine_);
     st_.fetch_buf_bytes = fetch_buf_;
     st_.uncomp_buf_bytes = uncomp_buf;
   }
@@ -756,7 +761,7 @@ void ReduceTask::fetch_phase(MergeQueue* q, int n, std::vector<std::string>* map
 
 void ReduceTask::merging_phase(MergeQueue* q) {
   std::vector<uint8_t> buf((size_t)kv_buf_size_);
-  KVWriter w(q);
+  KVWriter w(q, kind_, combine_);  // LPQ spills stay uncombined: the combiner runs where records are delivered
   bool done = false;
   while (!done) {
     if (stop_) throw UdaError("reduce task stopped during merge");
@@ -769,6 +774,10 @@ void ReduceTask::merging_phase(MergeQueue* q) {
   }
   std::lock_guard<std::mutex> g(st_mu_);
   st_.records += w.records();
+  if (combine_ != CombineOp::kNone) {
+    st_.combine_in_records += w.records_in();
+    st_.combine_groups += w.records();
+  }
 }
 
 void ReduceTask::merge_online() {
@@ -948,6 +957,8 @@ std::string ReduceTask::stats_json() const {
     << ",\"restored_maps\":" << s.restored_maps << ",\"device_descriptors\":" << s.device_descriptors << ",\"unmapped_descriptors\":" << s.unmapped_descriptors << ",\"unmapped_reason\":\"" << json_escape(s.unmapped_reason) << "\"" << ",\"descriptor_map_ms\":" << s.descriptor_map_ms << ",\"fetch_cmd_wait_ms\":" << s.fetch_cmd_wait_ms << ",\"fetch_ack_wait_ms\":" << s.fetch_ack_wait_ms << ",\"merge_start_boot_ms\":" << std::fixed << std::setprecision(1) << s.merge_start_boot_ms << ",\"fetch_sent_boot_ms\":" << s.fetch_sent_boot_ms << std::defaultfloat << std::setprecision(6) << ",\"first_data_ms\":" << s.first_data_ms << ",\"gpu_ws_bytes\":" << s.gpu_ws_bytes
     << ",\"host_fetched_bytes\":" << s.host_fetched_bytes << ",\"local_read_bytes\":" << s.local_read_bytes << ",\"hbm_wait_ms\":" << s.hbm_wait_ms
     << ",\"hbm_reserved\":" << s.hbm_reserved << ",\"round_bytes\":" << s.round_bytes << ",\"gpu_device\":" << s.gpu_device << ",\"merge_path\":\"" << s.merge_path << "\""
+    << ",\"combine\":\"" << s.combine << "\",\"combine_in_records\":" << s.combine_in_records
+    << ",\"combine_groups\":" << s.combine_groups
     << ",\"finished\":" << (finished_ ? "true" : "false") << "}";
   return o.str();
 }

@@ -23,6 +23,7 @@
 
 #include "uda/cmd.h"
 #include "uda/codec.h"
+#include "uda/combine.h"
 #include "uda/compare.h"
 #include "uda/host.h"
 #include "uda/ifile.h"
@@ -90,6 +91,11 @@ struct ReduceStats {
   int64_t host_fetched_bytes = 0;     // GPU device fetch: bytes of MOFs that were not device-resident
   int64_t local_read_bytes = 0;       // of those: read from the MOF files on this node (not over the network)
   std::string merge_path;             // which merge ran ("device-fixed10", "device-generic", ...)
+  // mapred.uda.merge.combine: "none", "sum.int", "sum.long", or "skipped-over-budget" when the GPU hybrid
+  // delivered the uncombined stream; merged records that went into the combiner and the groups (records)
+  // it delivered. records / bytes_delivered / buffers count what was delivered.
+  std::string combine = "none";
+  int64_t combine_in_records = 0, combine_groups = 0;
   std::string backend;
 };
 
@@ -191,6 +197,7 @@ class ReduceTask {
   std::string fault_spec_;             // mapred.uda.fault.inject (tests: faults of this task only)
   double hbm_budget_conf_ = 0;
   int delivery_pack_ = 2;                       // mapred.uda.gpu.delivery.pack: colpack version, 0 = off
+  CombineOp combine_ = CombineOp::kNone;        // mapred.uda.merge.combine
   int64_t delivery_piece_bytes_ = 64ll << 20;   // mapred.uda.gpu.delivery.piece.bytes
   int device_ = 0;
   int registry_slot_ = -1;

@@ -3,6 +3,7 @@
 
 #include <chrono>
 
+#include "uda/combine.h"
 #include "uda/error.h"
 
 namespace uda {
@@ -192,17 +193,41 @@ bool MergeQueue::next() {
 }
 
 // ---------------------------------------------------------------------------- KVWriter
+KVWriter::KVWriter(MergeQueue* q) : q_(q) {}
+KVWriter::KVWriter(MergeQueue* q, KeyKind kind, CombineOp op) : q_(q) {
+  if (op != CombineOp::kNone) comb_ = std::make_unique<StreamCombiner>(kind, op);
+}
+KVWriter::~KVWriter() = default;
+
+bool KVWriter::next_record() {
+  if (!comb_) {
+    if (!q_->next()) return false;
+    ++records_in_;
+    out_ = q_->cur();
+    return true;
+  }
+  while (!q_done_) {
+    if (!q_->next()) {
+      q_done_ = true;
+      return comb_->finish(&out_);
+    }
+    ++records_in_;
+    if (comb_->feed(q_->cur(), &out_)) return true;
+  }
+  return false;
+}
+
 bool KVWriter::fill(uint8_t* buf, int64_t cap, int64_t* len) {
   int64_t w = 0;
   for (;;) {
     if (!pending_) {
-      if (drained_ || !q_->next()) {
+      if (drained_ || !next_record()) {
         drained_ = true;
         break;
       }
       pending_ = true;
     }
-    const RecordView& r = q_->cur();
+    const RecordView& r = out_;
     const int64_t need = ifile_record_size(r.klen, r.vlen);
     if (need > cap) throw UdaError("record larger than the delivery buffer");
     if (w + need > cap) {

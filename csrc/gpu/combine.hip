@@ -1,0 +1,229 @@
+// Reduce-side combiner on the merged order (uda/combine.h: sum.int, sum.long): equal keys are adjacent
+// after F3, so what remains is a head flag per merged element, a segmented sum of the values and a
+// compaction in F4. Everything reads the side tables F2 left behind (keyptr / keylen / recptr / reclen);
+// record headers are never parsed again.
+//
+//   combine_heads_kernel    head[i] = first record of its group, and the value-length check
+//   (exclusive scan of head: gidx[i] = groups begun before i, so group(i) = gidx[i + 1] - 1)
+//   combine_sums_kernel     sums[group] = sum of the group's values, sizes[i] = head ? reclen : 0
+//   (exclusive scan of sizes: output offsets; a non-head shares the offset of the next head)
+//   gather_combine_kernel   copies the head records, their last W bytes replaced by the big-endian sum
+//
+// Sums are unsigned 64-bit integers (the low 32 bits serve sum.int): wrapping adds are associative, so
+// the result is the same bits in any reduction order, atomics included.
+#include "generic_cmp.h"
+#include "kernels.h"
+
+namespace uda {
+namespace gpu {
+
+namespace {
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 __attribute__((aligned(1))) u32x4_u;  // unaligned 16-byte access (legal for global memory)
+
+static_assert(kCombineTile == 256, "combine_sums_kernel: one element per lane, four waves per tile");
+
+// Equal under key_compare: the same content bytes and the same content length. Elem.hi holds content
+// bytes 0..7 zero padded, so the length has to match too ("a" and "a\0" share hi); the 16-bit length
+// field clamps at 0xFFFF, so contents longer than 8 bytes compare their real lengths in keylen.
+__device__ __forceinline__ bool same_key(const GenericKeyCtx& ctx, const Elem& a, const Elem& b) {
+  if (a.hi != b.hi || (a.lo >> 48) != (b.lo >> 48)) return false;
+  if ((a.lo >> 48) <= 8) return true;
+  const uint64_t ga = a.lo & kGenOrdMask, gb = b.lo & kGenOrdMask;
+  const int la = ctx.keylen[ga];
+  if (la != ctx.keylen[gb]) return false;
+  const uint8_t* pa = ctx.keyptr[ga];
+  const uint8_t* pb = ctx.keyptr[gb];
+  for (int i = 8; i < la; i += 8)
+    if (load_be8(pa + i, la - i) != load_be8(pb + i, la - i)) return false;
+  return true;
+}
+
+// Value bytes of record g from the side tables: record size less the headers, the key's class prefix
+// (both lie between recptr and keyptr) and the key content.
+__device__ __forceinline__ int64_t value_bytes(const GenericKeyCtx& ctx, uint64_t g) {
+  return (int64_t)ctx.reclen[g] - (int64_t)(ctx.keyptr[g] - ctx.recptr[g]) - (int64_t)ctx.keylen[g];
+}
+
+__global__ void __launch_bounds__(256) combine_heads_kernel(GenericKeyCtx ctx, const Elem* order, int64_t n, int W,
+                                                            int64_t* heads, unsigned long long* bad) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Elem e = order[i];
+  heads[i] = (i == 0 || !same_key(ctx, order[i - 1], e)) ? 1 : 0;
+  // error path only: the lowest merged position with a value the op cannot sum
+  if (value_bytes(ctx, e.lo & kGenOrdMask) != W) atomicMin(bad, (unsigned long long)i);
+}
+
+// One merged element per lane, kCombineTile per workgroup. A wave's values are summed by a segmented
+// inclusive scan under the wave's head mask, the waves' open ends are joined through LDS, and the last
+// lane of every segment that ends in the workgroup writes it. A group that lies inside the tile is written
+// with a plain store; the tile's leading segment (its head is in an earlier tile) and its trailing one
+// (it goes on in the next tile) are added to the zeroed sums[] with one atomic each.
+__global__ void __launch_bounds__(kCombineTile) combine_sums_kernel(GenericKeyCtx ctx, const Elem* order,
+                                                                    const int64_t* gidx, int64_t n, int W,
+                                                                    unsigned long long* sums, int64_t* sizes) {
+  constexpr int kWaves = kCombineTile / 64;
+  __shared__ unsigned long long tail[kWaves];
+  __shared__ int has_head[kWaves], first_head[kWaves];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t i = (int64_t)blockIdx.x * kCombineTile + threadIdx.x;
+  const bool valid = i < n;
+  bool h = true;  // lanes past the end close the last segment and write nothing
+  int64_t group = 0;
+  unsigned long long v = 0;
+  if (valid) {
+    const int64_t g0 = gidx[i], g1 = gidx[i + 1];
+    h = g1 != g0;
+    group = g1 - 1;
+    const uint64_t g = order[i].lo & kGenOrdMask;
+    const int L = ctx.reclen[g];
+    sizes[i] = h ? L : 0;
+    if (value_bytes(ctx, g) == W) {  // else: flagged by combine_heads_kernel, nothing is delivered
+      const uint8_t* p = ctx.recptr[g] + L - W;
+      if (W == 8) {
+        uint64_t w;
+        __builtin_memcpy(&w, p, 8);
+        v = __builtin_bswap64(w);
+      } else {
+        uint32_t w;
+        __builtin_memcpy(&w, p, 4);
+        v = __builtin_bswap32(w);
+      }
+    }
+  }
+  const unsigned long long mask = __ballot(h);
+  const unsigned long long below = mask & ((2ull << lane) - 1);  // heads at or before this lane
+  const bool open = below == 0;                                  // the segment began in an earlier wave
+  const int seg_lo = open ? 0 : 63 - __builtin_clzll(below);
+  unsigned long long x = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned long long y = __shfl_up(x, off, 64);
+    if (lane - off >= seg_lo) x += y;
+  }
+  if (lane == 63) tail[wid] = x;
+  if (lane == 0) {
+    has_head[wid] = mask != 0;
+    first_head[wid] = (int)(mask & 1);
+  }
+  __syncthreads();
+  if (!valid) return;
+  const bool seg_end = lane == 63 || ((mask >> (lane + 1)) & 1);
+  if (!seg_end) return;
+  if (lane == 63 && wid + 1 < kWaves && !first_head[wid + 1]) return;  // goes on in the next wave
+  bool head_in_tile = !open;
+  if (open) {  // the earlier waves' open ends, back to the nearest head
+    for (int w = wid - 1; w >= 0; --w) {
+      x += tail[w];
+      if (has_head[w]) {
+        head_in_tile = true;
+        break;
+      }
+    }
+  }
+  bool ends_in_tile = true;
+  if (lane == 63 && wid + 1 == kWaves && i + 1 < n) ends_in_tile = gidx[i + 2] != gidx[i + 1];
+  if (head_in_tile && ends_in_tile)
+    sums[group] = x;
+  else
+    atomicAdd(&sums[group], x);
+}
+
+// Bytes [t, t + W) of the 8 bytes in w (as loaded: byte k in bits 8k..8k+7) replaced by the sum's
+// big-endian bytes `be` (in the same layout; bm covers its W bytes). t may lie outside the word.
+__device__ __forceinline__ uint64_t patch8(uint64_t w, int t, uint64_t be, uint64_t bm) {
+  if (t >= 8 || t <= -8) return w;
+  const uint64_t v = t >= 0 ? be << (8 * t) : be >> (8 * -t);
+  const uint64_t m = t >= 0 ? bm << (8 * t) : bm >> (8 * -t);
+  return (w & ~m) | (v & m);
+}
+
+__device__ __forceinline__ u32x4 patch16(u32x4 v, int t, uint64_t be, uint64_t bm) {
+  if (t >= 16) return v;
+  const uint64_t lo = patch8((uint64_t)v[0] | ((uint64_t)v[1] << 32), t, be, bm);
+  const uint64_t hi = patch8((uint64_t)v[2] | ((uint64_t)v[3] << 32), t - 8, be, bm);
+  u32x4 r;
+  r[0] = (uint32_t)lo;
+  r[1] = (uint32_t)(lo >> 32);
+  r[2] = (uint32_t)hi;
+  r[3] = (uint32_t)(hi >> 32);
+  return r;
+}
+
+// F4 under combine: gather_var_grp_kernel's copy (kGatherLanes lanes per record, 16-byte pieces, the
+// last one shifted back to end at L) for the head records only. The sum replaces the record's last W
+// bytes in the registers of whichever pieces cover them, before the store: overlapping pieces then still
+// store identical bytes, and no second store has to be ordered after the copy.
+template <int kGatherLanes>
+__global__ void __launch_bounds__(256) gather_combine_kernel(GenericKeyCtx ctx, const Elem* elems, int64_t n,
+                                                             const int64_t* gidx, const int64_t* out_off,
+                                                             const unsigned long long* sums, int W, uint8_t* out) {
+  const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kGatherLanes;
+  const int sub = (int)(threadIdx.x % kGatherLanes);
+  if (i >= n) return;
+  const int64_t g1 = gidx[i + 1];
+  if (g1 == gidx[i]) return;  // not the head of its group
+  const uint64_t g = elems[i].lo & kGenOrdMask;
+  const uint8_t* src = ctx.recptr[g];
+  const int L = ctx.reclen[g];
+  uint8_t* dst = out + out_off[i];
+  const unsigned long long sum = sums[g1 - 1];
+  const uint64_t be = W == 8 ? __builtin_bswap64(sum) : (uint64_t)__builtin_bswap32((uint32_t)sum);
+  const uint64_t bm = W == 8 ? ~0ull : 0xFFFFFFFFull;
+  const int vt = L - W;  // the value's offset in the record
+  if (L < 16) {
+    if (sub != 0) return;
+    if (L >= 8) {
+      uint64_t a, b;
+      __builtin_memcpy(&a, src, 8);
+      __builtin_memcpy(&b, src + L - 8, 8);
+      a = patch8(a, vt, be, bm);
+      b = patch8(b, 8 - W, be, bm);
+      __builtin_memcpy(dst, &a, 8);
+      __builtin_memcpy(dst + L - 8, &b, 8);
+    } else {
+      for (int k = 0; k < L; ++k) dst[k] = k >= vt ? (uint8_t)(be >> (8 * (k - vt))) : src[k];
+    }
+    return;
+  }
+  constexpr int kStep = kGatherLanes * 16;
+  for (int base = sub * 16; base < L; base += 2 * kStep) {
+    const int o0 = min(base, L - 16);
+    const int o1 = min(base + kStep, L - 16);
+    const u32x4 v0 = patch16(*reinterpret_cast<const u32x4_u*>(src + o0), vt - o0, be, bm);
+    const u32x4 v1 = patch16(*reinterpret_cast<const u32x4_u*>(src + o1), vt - o1, be, bm);
+    *reinterpret_cast<u32x4_u*>(dst + o0) = v0;
+    if (base + kStep < L) *reinterpret_cast<u32x4_u*>(dst + o1) = v1;
+  }
+}
+
+}  // namespace
+
+void launch_combine_heads(GenericKeyCtx ctx, const Elem* order, int64_t n, int W, int64_t* heads,
+                          unsigned long long* bad, hipStream_t s) {
+  (void)hipMemsetAsync(bad, 0xFF, sizeof(unsigned long long), s);
+  if (n <= 0) return;
+  hipLaunchKernelGGL(combine_heads_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ctx, order, n, W,
+                     heads, bad);
+}
+
+void launch_combine_sums(GenericKeyCtx ctx, const Elem* order, const int64_t* gidx, int64_t n, int W,
+                         unsigned long long* sums, int64_t* sizes, hipStream_t s) {
+  if (n <= 0) return;
+  (void)hipMemsetAsync(sums, 0, (size_t)n * sizeof(unsigned long long), s);
+  hipLaunchKernelGGL(combine_sums_kernel, dim3((unsigned)((n + kCombineTile - 1) / kCombineTile)), dim3(kCombineTile),
+                     0, s, ctx, order, gidx, n, W, sums, sizes);
+}
+
+void launch_gather_combine(GenericKeyCtx ctx, const Elem* elems, int64_t n, const int64_t* gidx,
+                           const int64_t* out_off, const unsigned long long* sums, int W, uint8_t* out,
+                           hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(gather_combine_kernel<8>, dim3((unsigned)((n * 8 + 255) / 256)), dim3(256), 0, s, ctx, elems, n,
+                     gidx, out_off, sums, W, out);
+}
+
+}  // namespace gpu
+}  // namespace uda

@@ -1,6 +1,7 @@
 #include "generic_merger.h"
 #include "merge_plan.h"
 
+#include "uda/error.h"
 #include "uda/log.h"
 #include "uda/trace.h"
 
@@ -57,10 +58,17 @@ void GenericMerger::reserve(int64_t records, int runs) {
   cap_runs_ = std::max(runs, cap_runs_);
 }
 
+void GenericMerger::reserve_combine(int64_t records) {
+  records = std::max<int64_t>(records, 1);
+  if (gidx_.size() < (size_t)(records + 1) * 8) gidx_.alloc_local((size_t)(records + 1) * 8 + (size_t)records);
+  if (sums_.size() < (size_t)records * 8) sums_.alloc_local((size_t)records * 8 + (size_t)records);
+  if (cflag_.size() < 64) cflag_.alloc_local(64);
+}
+
 int64_t GenericMerger::workspace_bytes() const {
   int64_t b = 0;
   for (const DeviceBuffer* x : {&eoff_, &rounds_, &elems_a_, &elems_b_, &splits_, &sizes_, &out_off_, &scan_tmp_, &cuts_,
-                                &offsets_, &tables_, &side_, &ck_, &f1ws_})
+                                &offsets_, &tables_, &side_, &ck_, &f1ws_, &gidx_, &sums_, &cflag_})
     b += (int64_t)x->size();
   for (const auto& k : gk_)
     for (const DeviceBuffer* x : {&k.tab, &k.samp, &k.sa, &k.sb, &k.bounds, &k.split, &k.hist, &k.flag}) b += (int64_t)x->size();
@@ -143,7 +151,7 @@ bool GenericMerger::kway_level(int depth, const Elem* in, const std::vector<int6
 
 GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs, const std::vector<int64_t>& run_bytes,
                                         int kind, uint8_t* out, int64_t out_cap, int64_t kv_buf, hipStream_t s,
-                                        const RoundFn& on_round, int64_t round_bytes) {
+                                        const RoundFn& on_round, int64_t round_bytes, CombineOp combine) {
   trace::Range tr("uda.generic_merge");
   // UDA_GM_PROFILE=1: synchronize after each phase and print the split (diagnostic only)
   static const bool prof = std::getenv("UDA_GM_PROFILE") != nullptr;
@@ -265,6 +273,7 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
   const int64_t total = eoff[K];
   if (bytes > out_cap) throw std::runtime_error("GenericMerger: output capacity too small");
   res.records = total;
+  res.records_in = total;
   res.bytes = bytes;
   phase("f1_scan");
   reserve(std::max(total, nchunks), K);
@@ -326,11 +335,15 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
   // F4 for merged elements [e0, e0 + n) whose records start at output byte b0: sizes -> scan ->
   // gather, then the delivery cuts of that range (relative) into host `raw` (pinned; complete once
   // the stream passes this point). Enqueued only.
+  // (timed: the whole path's phase split under UDA_GM_PROFILE; the streamed rounds stay one phase)
   auto f4_enqueue = [&](const Elem* order, int64_t e0, int64_t n, int64_t b0, int64_t nbytes, int64_t chunk,
-                        int64_t* d_cuts, int64_t* raw) {
+                        int64_t* d_cuts, int64_t* raw, bool timed = false) {
     launch_record_sizes(ctx, order + e0, n, sizes_.as<int64_t>() + e0, s);
+    if (timed) phase("f4_record_sizes");
     launch_exclusive_scan(sizes_.as<int64_t>() + e0, out_off_.as<int64_t>() + e0, n, scan_tmp_.as<int64_t>(), s);
+    if (timed) phase("f4_scan");
     launch_gather_var(ctx, order + e0, n, out_off_.as<int64_t>() + e0, out + b0, s);
+    if (timed) phase("f4_gather_var");
     const int64_t nbuf = (nbytes + chunk - 1) / chunk;
     launch_buffer_cuts(out_off_.as<int64_t>() + e0, n, chunk, nbuf, d_cuts, s);
     HIP_CHECK(hipMemcpyAsync(raw, d_cuts, 8 * (nbuf + 1), hipMemcpyDeviceToHost, s));
@@ -347,7 +360,10 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
     if (cuts_host_.size() < (size_t)entries * 8) cuts_host_.alloc((size_t)entries * 8 + 4096);
   };
   int64_t C = 0;
-  if (gk && on_round && kway_level(0, cur, eoff, d_eoff, d_eoff, nxt, ctx, s, /*launch_cells=*/false, &C)) {
+  // (not under combine: a streamed round's bytes rb[q] come from input sizes, and a group of equal keys can
+  // straddle two cells, the order's tie-break being the ordinal)
+  if (combine == CombineOp::kNone && gk && on_round &&
+      kway_level(0, cur, eoff, d_eoff, d_eoff, nxt, ctx, s, /*launch_cells=*/false, &C)) {
     // ---- streamed: key-range rounds of cells; round q's output is handed over (on_round) while the
     // device merges round q + 1, so the caller's D2H overlaps the merge
     res.passes = 1;
@@ -422,12 +438,65 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
     }
     phase("f3_merge");
     const int64_t chunk = chunk_bytes(cur);
-    const int64_t nbuf = (bytes + chunk - 1) / chunk;
-    reserve_cuts(nbuf + 1);
-    f4_enqueue(cur, 0, total, 0, bytes, chunk, cuts_.as<int64_t>(), cuts_host_.as<int64_t>());
-    HIP_CHECK(hipStreamSynchronize(s));
-    absolute_cuts(cuts_host_.as<int64_t>(), nbuf, 0, bytes, &res.cuts);
-    if (on_round) on_round(res.cuts, total, true);
+    if (combine != CombineOp::kNone) {
+      // ---- F4 under combine (combine.hip): heads -> group index -> sums and sizes -> offsets; the
+      // compacted size is known only after the scans, so it is read here before the cuts are sized
+      const int W = combine_value_bytes(combine);
+      reserve_combine(total);
+      int64_t* d_gidx = gidx_.as<int64_t>();
+      auto* d_sums = sums_.as<unsigned long long>();
+      auto* d_bad = cflag_.as<unsigned long long>();
+      phase("f4_chunk");
+      launch_combine_heads(ctx, cur, total, W, sizes_.as<int64_t>(), d_bad, s);
+      phase("f4c_heads");
+      launch_exclusive_scan(sizes_.as<int64_t>(), d_gidx, total, scan_tmp_.as<int64_t>(), s);
+      phase("f4c_group_scan");
+      launch_combine_sums(ctx, cur, d_gidx, total, W, d_sums, sizes_.as<int64_t>(), s);
+      phase("f4c_sums");
+      launch_exclusive_scan(sizes_.as<int64_t>(), out_off_.as<int64_t>(), total, scan_tmp_.as<int64_t>(), s);
+      phase("f4_scan");
+      unsigned long long bad = 0;
+      int64_t groups = 0, cbytes = 0;
+      HIP_CHECK(hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(&groups, d_gidx + total, 8, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(&cbytes, out_off_.as<int64_t>() + total, 8, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      if (bad != ~0ull) {
+        // the first record (in merged order) the op cannot sum: its key and value length for the error
+        Elem e;
+        HIP_CHECK(hipMemcpy(&e, cur + bad, sizeof(Elem), hipMemcpyDeviceToHost));
+        const uint64_t g = e.lo & 0xFFFFFFFFFFFFull;
+        const uint8_t *rp = nullptr, *kp = nullptr;
+        int32_t rl = 0, kl = 0;
+        HIP_CHECK(hipMemcpy(&rp, ctx.recptr + g, 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(&kp, ctx.keyptr + g, 8, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(&rl, ctx.reclen + g, 4, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(&kl, ctx.keylen + g, 4, hipMemcpyDeviceToHost));
+        const int64_t vlen = (int64_t)rl - (kp - rp) - kl;
+        std::vector<uint8_t> key((size_t)std::min<int32_t>(kl, 64));
+        if (!key.empty()) HIP_CHECK(hipMemcpy(key.data(), kp, key.size(), hipMemcpyDeviceToHost));
+        throw UdaError(combine_bad_value_message(combine, key.data(), (int64_t)key.size(), vlen));
+      }
+      res.records = groups;
+      res.bytes = cbytes;
+      const int64_t nbuf = (cbytes + chunk - 1) / chunk;
+      reserve_cuts(nbuf + 1);
+      launch_gather_combine(ctx, cur, total, d_gidx, out_off_.as<int64_t>(), d_sums, W, out, s);
+      phase("f4c_gather_combine");
+      launch_buffer_cuts(out_off_.as<int64_t>(), total, chunk, nbuf, cuts_.as<int64_t>(), s);
+      HIP_CHECK(hipMemcpyAsync(cuts_host_.as<int64_t>(), cuts_.as<int64_t>(), 8 * (nbuf + 1), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      absolute_cuts(cuts_host_.as<int64_t>(), nbuf, 0, cbytes, &res.cuts);
+      if (on_round) on_round(res.cuts, groups, true);
+    } else {
+      const int64_t nbuf = (bytes + chunk - 1) / chunk;
+      reserve_cuts(nbuf + 1);
+      phase("f4_chunk");
+      f4_enqueue(cur, 0, total, 0, bytes, chunk, cuts_.as<int64_t>(), cuts_host_.as<int64_t>(), /*timed=*/true);
+      HIP_CHECK(hipStreamSynchronize(s));
+      absolute_cuts(cuts_host_.as<int64_t>(), nbuf, 0, bytes, &res.cuts);
+      if (on_round) on_round(res.cuts, total, true);
+    }
   }
   phase("f4_gather_cuts");
   if (prof) {

@@ -9,12 +9,14 @@
 
 #include "device_engine.h"
 #include "kernels.h"
+#include "uda/combine.h"
 
 namespace uda {
 namespace gpu {
 
 struct GenericMergeResult {
-  int64_t records = 0;
+  int64_t records = 0;     // records written to the output (under combine: one per group of equal keys)
+  int64_t records_in = 0;  // records merged
   int64_t bytes = 0;     // merged record bytes (no EOF marker)
   int passes = 0;
   std::vector<int64_t> cuts;  // delivery buffer boundaries as byte offsets into the output (0 .. bytes)
@@ -35,10 +37,16 @@ class GenericMerger {
   // complete: on_round(cuts, records, last) with absolute cuts of that round's delivery buffers, called
   // on this thread while the device already merges the next round (so a caller's D2H of the round
   // overlaps the merge). Without the single-pass path it is called once for the whole output.
+  //
+  // combine (uda/combine.h): equal keys are summed into their group's first record before the gather
+  // (combine.hip); the output then holds one record per distinct key of the runs, and on_round is called
+  // once (the output's size is known only after the group scan). A record whose value the op cannot sum
+  // throws UdaError and nothing is written. kNone: the merge as it is without a combiner.
   using RoundFn = std::function<void(const std::vector<int64_t>& cuts, int64_t records, bool last)>;
   GenericMergeResult merge(const std::vector<const uint8_t*>& runs, const std::vector<int64_t>& run_bytes,
                            int kind, uint8_t* out, int64_t out_cap, int64_t kv_buf, hipStream_t s,
-                           const RoundFn& on_round = nullptr, int64_t round_bytes = 256ll << 20);
+                           const RoundFn& on_round = nullptr, int64_t round_bytes = 256ll << 20,
+                           CombineOp combine = CombineOp::kNone);
 
   // runs the last merge indexed with the serial F1 walk (records longer than the parallel entry table)
   int f1_serial_runs() const { return f1_serial_runs_; }
@@ -48,6 +56,9 @@ class GenericMerger {
  private:
   int f1_serial_runs_ = 0;
   void reserve(int64_t records, int runs);
+  // combine workspace: group index (8 B) and sums (8 B) per record, the bad-value flag
+  void reserve_combine(int64_t records);
+  DeviceBuffer gidx_, sums_, cflag_;
   DeviceBuffer eoff_, rounds_, passtab_;  // passtab_: pairwise-tree pass tables (no hipMalloc/hipFree per merge)
   PinnedBuffer cuts_host_;
   std::vector<hipEvent_t> round_ev_;

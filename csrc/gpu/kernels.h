@@ -219,6 +219,27 @@ void launch_max_i32(const int32_t* v, int64_t n, unsigned int* out, hipStream_t 
 void launch_buffer_cuts(const int64_t* out_off, int64_t n, int64_t chunk, int64_t nbuf, int64_t* cuts,
                         hipStream_t s);
 
+// ---------------------------------------------------------------- reduce-side combiner (combine.hip)
+// Equal keys of the merged order summed into their group's first record (uda/combine.h); W = 4
+// (sum.int) or 8 (sum.long) value bytes.
+constexpr int kCombineTile = 256;  // merged elements per workgroup of launch_combine_sums
+// heads[i] = 1 if merged element i starts a group (i == 0 or its key differs from i - 1's), else 0.
+// *bad = lowest i whose record's value is not W bytes long, ~0 if none (set here).
+void launch_combine_heads(GenericKeyCtx ctx, const Elem* order, int64_t n, int W, int64_t* heads,
+                          unsigned long long* bad, hipStream_t s);
+// gidx = exclusive scan of heads (n + 1 entries). sums[q] = sum of the values of group q modulo 2^64
+// (n entries of room, zeroed here; values of records flagged in *bad count as 0), and the F4 sizes
+// under combine: sizes[i] = record size of a head, 0 for any other element.
+void launch_combine_sums(GenericKeyCtx ctx, const Elem* order, const int64_t* gidx, int64_t n, int W,
+                         unsigned long long* sums, int64_t* sizes, hipStream_t s);
+// F4 under combine: the head records copied to out + out_off[i] (out_off = exclusive scan of those
+// sizes), their last W bytes replaced by the big-endian low 8W bits of their group's sum.
+// launch_buffer_cuts runs on these offsets unchanged: an element of size 0 has the offset of the next
+// head (or the total), so the first offset >= j * chunk it finds is still a record boundary.
+void launch_gather_combine(GenericKeyCtx ctx, const Elem* elems, int64_t n, const int64_t* gidx,
+                           const int64_t* out_off, const unsigned long long* sums, int W, uint8_t* out,
+                           hipStream_t s);
+
 // ---------------------------------------------------------------- gather / serialize (F4)
 // out[i*104 .. +104) = record of elem[i] (FIXED10: run/pos encoded in elem.lo).
 void launch_gather_fixed(const Elem* elems, int64_t n, uint8_t* const* run_bases, uint8_t* out,

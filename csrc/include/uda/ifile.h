@@ -121,18 +121,30 @@ class MergeQueue {
 // buffer holds whole records; a record that does not fit stays pending for the next buffer; after
 // the last record the EOF marker is appended if it fits, otherwise it goes alone into the next
 // buffer. fill() returns true once the EOF marker has been written.
+//
+// With a combine op (uda/combine.h) the writer packs one record per group of equal keys instead: the
+// merged records pass through a StreamCombiner on their way into the buffers.
+enum class CombineOp : int;
+class StreamCombiner;
 class KVWriter {
  public:
-  explicit KVWriter(MergeQueue* q) : q_(q) {}
+  explicit KVWriter(MergeQueue* q);
+  KVWriter(MergeQueue* q, KeyKind kind, CombineOp op);
+  ~KVWriter();
   bool fill(uint8_t* buf, int64_t cap, int64_t* len);
-  int64_t records() const { return records_; }
+  int64_t records() const { return records_; }        // records written (groups under combine)
+  int64_t records_in() const { return records_in_; }  // merged records consumed
   int64_t bytes() const { return bytes_; }
 
  private:
+  bool next_record();  // the next record to write into out_
   MergeQueue* q_;
+  std::unique_ptr<StreamCombiner> comb_;
+  RecordView out_;
   bool pending_ = false;
   bool drained_ = false;
-  int64_t records_ = 0, bytes_ = 0;
+  bool q_done_ = false;
+  int64_t records_ = 0, records_in_ = 0, bytes_ = 0;
 };
 
 }  // namespace uda

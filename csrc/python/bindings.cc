@@ -224,8 +224,14 @@ struct PyBridge {
   }
 };
 
+CombineOp combine_op_arg(const std::string& v) {
+  CombineOp op;
+  if (!combine_op_from_conf(v, &op)) throw py::value_error("unknown combine \"" + v + "\" (" + kCombineAllowed + ")");
+  return op;
+}
+
 py::bytes cpu_merge_impl(const std::vector<std::string>& runs, const std::string& key_class, int64_t buf,
-                         std::vector<int64_t>* lens) {
+                         std::vector<int64_t>* lens, CombineOp combine = CombineOp::kNone) {
   KeyKind kind = key_kind_from_class(key_class.c_str());
   if (kind == KeyKind::kUnsupported) throw py::value_error("unsupported key class");
   MergeQueue q(kind);
@@ -234,7 +240,7 @@ py::bytes cpu_merge_impl(const std::vector<std::string>& runs, const std::string
     seg->index = (int)i;
     q.insert(std::move(seg));
   }
-  KVWriter w(&q);
+  KVWriter w(&q, kind, combine);
   std::string out;
   std::vector<uint8_t> b((size_t)buf);
   bool done = false;
@@ -639,11 +645,22 @@ PYBIND11_MODULE(_uda_native, m) {
   });
 
   // ---------------------------------------------------------------- CPU engine
-  m.def("cpu_merge", [](const std::vector<std::string>& runs, const std::string& key_class, int64_t buf) {
+  m.def("cpu_merge", [](const std::vector<std::string>& runs, const std::string& key_class, int64_t buf,
+                        const std::string& combine) {
     std::vector<int64_t> lens;
-    py::bytes out = cpu_merge_impl(runs, key_class, buf, &lens);
+    py::bytes out = cpu_merge_impl(runs, key_class, buf, &lens, combine_op_arg(combine));
     return py::make_tuple(out, lens);
-  });
+  }, py::arg("runs"), py::arg("key_class"), py::arg("buf"), py::arg("combine") = "none");
+  // Host reference of the reduce-side combiner (uda/combine.h) over a stream already in merged order.
+  m.def("combine_stream", [](const std::string& stream, const std::string& key_class, const std::string& op) {
+    KeyKind kind = key_kind_from_class(key_class.c_str());
+    if (kind == KeyKind::kUnsupported) throw py::value_error("unsupported key class");
+    const std::vector<uint8_t> out =
+        combine_stream(reinterpret_cast<const uint8_t*>(stream.data()), stream.size(), kind, combine_op_arg(op));
+    return py::bytes(reinterpret_cast<const char*>(out.data()), out.size());
+  }, py::arg("stream"), py::arg("key_class"), py::arg("op"));
+  // merged elements per workgroup of the device combiner's segmented sum (tests build groups around it)
+  m.def("combine_tile", [] { return (int)gpu::kCombineTile; });
 
   // teravalidate: framing + order + checksum of a delivered stream, fed buffer by buffer
   py::class_<StreamValidator, std::shared_ptr<StreamValidator>>(m, "StreamValidator")
@@ -1432,10 +1449,13 @@ PYBIND11_MODULE(_uda_native, m) {
     return d;
   });
   // Merge IFile runs (any bytes-like objects, read in place) on the device. Returns
-  // (merged bytes, buffer cuts, records, merge passes, device merge ms, runs indexed serially).
-  m.def("gpu_merge_runs", [](const py::list& runs, const std::string& key_class, int64_t kv_buf, int device) {
+  // (merged bytes, buffer cuts, records, merge passes, device merge ms, runs indexed serially, records merged).
+  // combine: "none", "sum.int" or "sum.long" (uda/combine.h): records then counts the groups delivered.
+  m.def("gpu_merge_runs", [](const py::list& runs, const std::string& key_class, int64_t kv_buf, int device,
+                             const std::string& combine) {
     KeyKind kind = key_kind_from_class(key_class.c_str());
     if (kind == KeyKind::kUnsupported) throw py::value_error("unsupported key class");
+    const CombineOp cop = combine_op_arg(combine);
     std::vector<py::buffer_info> views;
     std::vector<const uint8_t*> host;
     std::vector<int64_t> bytes;
@@ -1447,11 +1467,17 @@ PYBIND11_MODULE(_uda_native, m) {
       total += bytes.back();
     }
     std::vector<int64_t> cuts;
-    int64_t records = 0, out_bytes = 0;
+    int64_t records = 0, records_in = 0, out_bytes = 0;
     int passes = 0, serial_runs = 0;
     double merge_ms = 0;
     gpu::DeviceBuffer in, dout;
     hipStream_t s = nullptr;
+    struct StreamDrop {  // a merge that throws (a value the combiner cannot sum) leaves no stream behind
+      hipStream_t& s;
+      ~StreamDrop() {
+        if (s) (void)hipStreamDestroy(s);
+      }
+    } stream_drop{s};
     {
       py::gil_scoped_release rel;
       HIP_CHECK(hipSetDevice(device));
@@ -1475,11 +1501,12 @@ PYBIND11_MODULE(_uda_native, m) {
       gpu::GenericMerger& gm = *gm_slot;
       HIP_CHECK(hipStreamSynchronize(s));
       auto t0 = std::chrono::steady_clock::now();
-      auto res = gm.merge(ptrs, bytes, (int)kind, dout.as<uint8_t>(), total, kv_buf, s);
+      auto res = gm.merge(ptrs, bytes, (int)kind, dout.as<uint8_t>(), total, kv_buf, s, nullptr, 256ll << 20, cop);
       HIP_CHECK(hipStreamSynchronize(s));
       merge_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
       cuts = res.cuts;
       records = res.records;
+      records_in = res.records_in;
       passes = res.passes;
       out_bytes = res.bytes;
       serial_runs = gm.f1_serial_runs();
@@ -1494,11 +1521,13 @@ PYBIND11_MODULE(_uda_native, m) {
       if (out_bytes) HIP_CHECK(hipMemcpyAsync(PyBytes_AS_STRING(o), dout.as(), (size_t)out_bytes, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
       HIP_CHECK(hipStreamDestroy(s));
+      s = nullptr;
       in.reset();
       dout.reset();
     }
-    return py::make_tuple(out, cuts, records, passes, merge_ms, serial_runs);
-  }, py::arg("runs"), py::arg("key_class"), py::arg("kv_buf") = 1 << 20, py::arg("device") = 0);
+    return py::make_tuple(out, cuts, records, passes, merge_ms, serial_runs, records_in);
+  }, py::arg("runs"), py::arg("key_class"), py::arg("kv_buf") = 1 << 20, py::arg("device") = 0,
+        py::arg("combine") = "none");
   // F8: sort TeraSort records (104-byte IFile records, no EOF marker) by their 10-byte key on the
   // device; returns (sorted bytes, device ms of the sort).
   m.def("gpu_sort_fixed", [](py::buffer b, int device, bool staged) {

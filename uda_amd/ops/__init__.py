@@ -15,17 +15,20 @@ last_stats: dict = {}  # timing of the most recent merge_runs call (device merge
 
 
 def merge_runs(runs: list[bytes], key_class: str, device: str = "gpu", kv_buf: int = 1 << 20,
-               gpu_index: int = 0):
+               gpu_index: int = 0, combine: str = "none"):
+    """combine: "none", "sum.int" or "sum.long" (mapred.uda.merge.combine): equal keys are summed into the
+    first record of their group, on the device (csrc/gpu/combine.hip) or by the host reference."""
     n = native()
     if device == "gpu":
         if n.device_count() <= 0:
             raise RuntimeError("merge_runs(device='gpu'): no HIP device visible")
-        merged, cuts, _records, _passes, merge_ms, serial = n.gpu_merge_runs(list(runs), key_class, kv_buf - 2,
-                                                                             gpu_index)
-        last_stats.update(device="gpu", records=_records, passes=_passes, merge_ms=merge_ms, f1_serial_runs=serial)
+        merged, cuts, _records, _passes, merge_ms, serial, records_in = n.gpu_merge_runs(
+            list(runs), key_class, kv_buf - 2, gpu_index, combine)
+        last_stats.update(device="gpu", records=_records, passes=_passes, merge_ms=merge_ms, f1_serial_runs=serial,
+                          records_in=records_in)
         return merged, cuts
     if device == "cpu":
-        out, lens = n.cpu_merge(list(runs), key_class, kv_buf)
+        out, lens = n.cpu_merge(list(runs), key_class, kv_buf, combine)
         # cpu_merge already appended the EOF marker and packed greedily
         body = out[:-2]
         cuts, pos = [0], 0
