@@ -30,7 +30,6 @@
 namespace uda {
 
 namespace {
-constexpr int kProgressReportLimit = 20;  // PROGRESS_REPORT_LIMIT (MergeManager.cc:44)
 constexpr int kExtraBuffers = 10;         // EXTRA_RDMA_BUFFERS (reducer.cc:50)
 constexpr int kMinParallelLpqs = 3;       // MIN_PARALLEL_LPQS (MergeManager.h:125)
 
@@ -705,6 +704,56 @@ std::unique_ptr<Segment> ReduceTask::segment_for(std::shared_ptr<MofFetcher> f, 
   return seg;
 }
 
+// GPU LPQ checkpoint (gpu_merge_staged.cc): the sparse index of a checkpointed spill file.
+// <spill>.idx: int64 n, then n x {int64 cut, int32 key length, key bytes}
+void write_lpq_index(const std::string& ip, const std::vector<int64_t>& idx_cut, const std::vector<std::string>& idx_key) {
+  std::string ix;
+  const int64_t n = (int64_t)idx_cut.size();
+  ix.append(reinterpret_cast<const char*>(&n), 8);
+  for (size_t j = 0; j < idx_cut.size(); ++j) {
+    const int32_t kl = (int32_t)idx_key[j].size();
+    ix.append(reinterpret_cast<const char*>(&idx_cut[j]), 8);
+    ix.append(reinterpret_cast<const char*>(&kl), 4);
+    ix.append(idx_key[j].data(), (size_t)kl);
+  }
+  const int ifd = create_private_file(ip, O_WRONLY);
+  const bool ok = ifd >= 0 && write_all(ifd, ix.data(), ix.size()) && ::fsync(ifd) == 0;
+  if (ifd >= 0) ::close(ifd);
+  if (!ok) throw UdaError("cannot write LPQ index " + ip);
+}
+
+void read_lpq_index(const std::string& ip, std::vector<int64_t>* cut, std::vector<std::string>* key) {
+  std::ifstream ix(ip, std::ios::binary);
+  int64_t n = -1;
+  ix.read(reinterpret_cast<char*>(&n), 8);
+  if (!ix || n < 0) throw UdaError("bad LPQ index " + ip);
+  for (int64_t j = 0; j < n; ++j) {
+    int64_t c = 0;
+    int32_t kl = 0;
+    ix.read(reinterpret_cast<char*>(&c), 8);
+    ix.read(reinterpret_cast<char*>(&kl), 4);
+    if (!ix || kl < 0) throw UdaError("bad LPQ index " + ip);
+    std::string k((size_t)kl, '\0');
+    ix.read(&k[0], kl);
+    cut->push_back(c);
+    key->push_back(std::move(k));
+  }
+}
+
+void ReduceTask::note_map_fetched(int64_t bytes) {
+  progress_count_++;
+  total_count_++;
+  {
+    std::lock_guard<std::mutex> g(st_mu_);
+    st_.maps_fetched++;
+    if (bytes) st_.bytes_fetched += bytes;
+  }
+  if (progress_count_ == kProgressReportLimit || total_count_ == init_.num_maps) {
+    host_->fetch_over();
+    progress_count_ = 0;
+  }
+}
+
 void ReduceTask::fetch_phase(MergeQueue* q, int n, std::vector<std::string>* map_ids) {
   std::mt19937_64 rng((uint64_t)std::chrono::steady_clock::now().time_since_epoch().count());
   int sent = 0, inserted = 0;
@@ -740,16 +789,7 @@ void ReduceTask::fetch_phase(MergeQueue* q, int n, std::vector<std::string>* map
       if (map_ids) map_ids->push_back(f->params().map_id);
       q->insert(segment_for(f, next_index_++));
       inserted++;
-      total_count_++;
-      progress_count_++;
-      {
-        std::lock_guard<std::mutex> g(st_mu_);
-        st_.maps_fetched++;
-      }
-      if (progress_count_ == kProgressReportLimit || total_count_ == init_.num_maps) {
-        host_->fetch_over();
-        progress_count_ = 0;
-      }
+      note_map_fetched();
     }
   }
   // requests not needed by this phase go back to the shared list (hybrid: next LPQ)

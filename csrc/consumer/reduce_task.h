@@ -6,8 +6,8 @@
 //   merge_do_fetching_phase / merge_do_merging_phase / merge_online / fetch_lpqs / merge_hybrid
 //   (src/Merger/MergeManager.cc:47-314)
 // Backends: "cpu" (heap k-way merge, the reference algorithm) and "gpu" (whole partitions staged in
-// HBM and merged by the HIP merge tree; csrc/consumer/gpu_merge.cc), chosen with
-// mapred.uda.merge.backend.
+// HBM and merged by the HIP merge tree; csrc/consumer/gpu_merge_staged.cc, gpu_merge_device.cc), chosen
+// with mapred.uda.merge.backend.
 #pragma once
 #include <atomic>
 #include <condition_variable>
@@ -32,6 +32,7 @@
 namespace uda {
 
 class MofFetcher;
+class StagedMerge;
 namespace gpu {
 class DeviceBuffer;
 }
@@ -105,6 +106,11 @@ struct ReduceStats {
 bool mof_host_is_local(const std::string& host_spec);
 int open_local_mof(const std::string& path, int64_t off, int64_t len);
 
+// The sparse index of a checkpointed GPU LPQ spill file (<spill>.idx): the record-boundary offsets and the
+// key at each. Written durably (fsync) before the manifest lists the spill; both throw on failure.
+void write_lpq_index(const std::string& path, const std::vector<int64_t>& cut, const std::vector<std::string>& key);
+void read_lpq_index(const std::string& path, std::vector<int64_t>* cut, std::vector<std::string>* key);
+
 // File confinement of a reduce task that runs on behalf of another local user (a merge-service session
 // whose client's uid is not the service's): what the task creates, reads back and unlinks must stay in the
 // node's own local directories, and it trusts only files this process's user owns.
@@ -117,6 +123,8 @@ std::string sandbox_check_dir(const std::vector<std::string>& roots, const std::
 // A file the task may read back / unlink: a regular file (not a symlink) owned by this process's euid
 // inside one of `dirs`.
 bool sandbox_trusted_file(const std::vector<std::string>& dirs, const std::string& path);
+
+constexpr int kProgressReportLimit = 20;  // PROGRESS_REPORT_LIMIT (MergeManager.cc:44)
 
 class ReduceTask {
  public:
@@ -201,6 +209,9 @@ class ReduceTask {
   int64_t delivery_piece_bytes_ = 64ll << 20;   // mapred.uda.gpu.delivery.piece.bytes
   int device_ = 0;
   int registry_slot_ = -1;
+  // One more map output is in: counts it and reports progress to the host (fetch_over) every
+  // kProgressReportLimit maps and at the last one. bytes: added to bytes_fetched (device fetch).
+  void note_map_fetched(int64_t bytes = 0);
   // Fetch `n` MOFs into `q` (reference merge_do_fetching_phase).
   void fetch_phase(MergeQueue* q, int n, std::vector<std::string>* map_ids = nullptr);
   // LPQ checkpoint (mapred.uda.lpq.checkpoint): completed LPQ spill files survive a failed attempt,
@@ -255,6 +266,7 @@ class ReduceTask {
   mutable std::mutex st_mu_;
   ReduceStats st_;
   friend class MofFetcher;
+  friend class StagedMerge;  // merge_gpu() as an object (gpu_merge_staged.cc)
 };
 
 // Pulls one MOF partition chunk by chunk with one request in flight ahead of the consumer

@@ -155,7 +155,7 @@ class FixedWsPool {
     return n;
   }
   // the idle workspace last used by the task most like this one (closest pool_key = input bytes; ties
-  // to the larger; key < 0: any), as DevicePool::acquire_fit in gpu_merge.cc
+  // to the larger; key < 0: any), as DevicePool::acquire_fit in gpu_workspace.h
   std::unique_ptr<FixedWs> acquire(int device, int64_t key = -1) {
     {
       std::lock_guard<std::mutex> g(mu_);

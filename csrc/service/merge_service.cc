@@ -680,7 +680,7 @@ struct RemoteReduceTask::Impl {
         const int node = p.size() >= 20 ? get<int32_t>(p, 16) : -1;
         if (node >= 0 && node != bound_node) {
           // dataFromUda copies out of these pages: run where they live, as the in-process delivery
-          // thread does (gpu_merge.cc binds it to the GPU's node)
+          // thread does (gpu_workspace.h binds it to the GPU's node)
           gpu::bind_thread_to_numa(node);
           bound_node = node;
         }
