@@ -16,6 +16,8 @@
                       job exceeds HBM): rounds are streamed H2D, merged on the GPU, delivered D2H.
   combine             wordcount over HBM-resident MOFs, 16 concurrent reduce tasks, 16 and 64 maps:
                       mapred.uda.merge.combine none vs sum.int, and the F4 kernels phase by phase.
+                      --vocab N --tasks N --maps N: one low-duplication, few-task shape (several inner
+                      rounds per task); --over-budget: the GPU hybrid, skipping against combining.
 
 Each prints one JSON line per result. Data is synthetic (native generators, csrc/engine/datagen.cc).
 """
@@ -457,20 +459,53 @@ def radix(args) -> dict:
             "hbm_gbps_est": round(moved / ms / 1e6, 1), "matches_numpy_lexsort": bool(ok)}
 
 
-def _combine_tasks(n, maps: int, tasks: int, rows: int, op: str, steps: int, warmup: int) -> dict:
-    """`tasks` concurrent reduce tasks over HBM-resident wordcount MOFs, `warmup` + `steps` times."""
+def _uniform_wordcount_runs(maps: int, tasks: int, rows: int, vocab: int, seed: int = 7):
+    """(word, 1) runs like the native wordcount generator's, but with words drawn uniformly from `vocab`
+    (the native one is Zipf over 100 000 words: hundreds of records per key). About vocab * (1 - exp(-R /
+    vocab)) distinct keys among the R records of the job: vocab = R / 1.6 leaves about R / 2 groups. Records
+    are 17 bytes: Text("w" + 9 digits) -> IntWritable(1), partitioned by word % tasks, sorted."""
+    import numpy as np
+    out = []
+    for m in range(maps):
+        w = np.random.default_rng(seed * 1000003 + m).integers(0, vocab, size=rows, dtype=np.int64)
+        parts = []
+        for r in range(tasks):
+            k = np.sort(w[w % tasks == r])
+            rec = np.zeros((len(k), 17), dtype=np.uint8)
+            rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3], rec[:, 16] = 0x0B, 0x04, 0x0A, ord("w"), 1
+            for j in range(9):
+                rec[:, 12 - j] = 48 + (k // 10 ** j) % 10
+            parts.append(rec.tobytes() + b"\xff\xff")
+        out.append(parts)
+    return out
+
+
+def _combine_tasks(n, maps: int, tasks: int, rows: int, op: str, steps: int, warmup: int, vocab: int = 0,
+                   over_budget: str = "", lpq: bool = False) -> dict:
+    """`tasks` concurrent reduce tasks over HBM-resident wordcount MOFs, `warmup` + `steps` times.
+    over_budget ("skip" | "combine"): the MOFs in host memory instead and mapred.uda.gpu.merge.bytes at a
+    quarter of a task's input, so every task takes the over-budget GPU hybrid (lpq: with LPQ spills in DRAM
+    instead of RPQ rounds straight over the partitions)."""
     from uda_amd.bridge import UdaConsumer, UdaProvider
     from uda_amd.utils.datagen import TEXT
     from uda_amd.utils.mof import encode_partitions
-    runs = n.generate_runs("wordcount", maps, tasks, rows, 7)
+    runs = _uniform_wordcount_runs(maps, tasks, rows, vocab) if vocab else n.generate_runs("wordcount", maps, tasks, rows, 7)
     prov = UdaProvider()
     total = 0
     for m, parts in enumerate(runs):
         data, index = encode_partitions(parts)
         total += len(data) - 2 * len(parts)
-        prov.add_mof_device("job_cb", f"attempt_cb_m_{m:06d}_0", data, index)
+        if over_budget:
+            prov.add_mof_memory("job_cb", f"attempt_cb_m_{m:06d}_0", data, index)
+        else:
+            prov.add_mof_device("job_cb", f"attempt_cb_m_{m:06d}_0", data, index)
     del runs
     conf = {"mapred.uda.merge.backend": "gpu", "mapred.uda.gpu.fetch": "device", "mapred.uda.merge.combine": op}
+    if over_budget:
+        conf = {"mapred.uda.merge.backend": "gpu", "mapred.uda.merge.combine": op, "mapred.uda.gpu.spill": "host",
+                "mapred.uda.gpu.merge.bytes": total // tasks // 4, "mapred.uda.merge.combine.over.budget": over_budget}
+        if lpq:
+            conf["mapred.uda.gpu.hybrid.direct"] = 0
     gbps, last = [], None
     for step in range(warmup + steps):
         cons = [UdaConsumer(maps, "job_cb", f"attempt_cb_r_{r:06d}_{step}", TEXT, conf=conf, keep_records=False)
@@ -494,6 +529,10 @@ def _combine_tasks(n, maps: int, tasks: int, rows: int, op: str, steps: int, war
             "merge_path": sorted({st["merge_path"] for st in last}),
             "combine_in_records": sum(st.get("combine_in_records", 0) for st in last),
             "combine_groups": sum(st.get("combine_groups", 0) for st in last),
+            "merge_rounds": sum(st.get("merge_rounds", 0) for st in last),
+            "rpq_rounds": sum(st.get("rpq_rounds", 0) for st in last), "lpqs": sum(st.get("lpqs", 0) for st in last),
+            "spill_bytes": sum(st.get("spill_bytes", 0) for st in last),
+            "task_d2h_wait_ms": [round(st["gpu_d2h_wait_ms"], 2) for st in last][:16],
             "task_mean_ms": {k: mean(k) for k in ("gpu_device_ms", "gpu_d2h_wait_ms", "gpu_sink_ms", "merge_ms")}}
 
 
@@ -521,16 +560,29 @@ def combine(args) -> dict:
     import subprocess
     from uda_amd import native
     n = native()
-    out = {"config": "wordcount, 16 reduce tasks over HBM-resident MOFs, combine none vs sum.int", "tasks": 16}
-    for maps in (16, 64):
+    tasks = args.tasks or 16
+    out = {"config": f"wordcount, {tasks} reduce tasks over HBM-resident MOFs, combine none vs sum.int", "tasks": tasks}
+    if args.over_budget:
+        # one shape, sum.int: the over-budget hybrid delivering the uncombined stream against combining
+        rows = int(args.gb * 1e9 / args.maps / 17)
+        out["config"] = f"wordcount, {tasks} reduce task(s) over host MOFs, device budget a quarter of the input"
+        for mode in ("skip", "combine"):
+            out[f"over_budget_{mode}"] = _combine_tasks(n, args.maps, tasks, rows, "sum.int", steps=5, warmup=2,
+                                                        vocab=args.vocab, over_budget=mode, lpq=args.lpq)
+            print(f"# over budget, {mode}: {json.dumps(out[f'over_budget_{mode}'])}", file=sys.stderr, flush=True)
+        return out
+    shaped = bool(args.vocab or args.tasks)  # --vocab / --tasks: that one shape (--maps), task level only
+    for maps in ((args.maps,) if shaped else (16, 64)):
         rows = int(args.gb * 1e9 / maps / 17)
         for op in ("none", "sum.int"):
-            r = _combine_tasks(n, maps, 16, rows, op, steps=5, warmup=2)
+            r = _combine_tasks(n, maps, tasks, rows, op, steps=5, warmup=2, vocab=args.vocab)
             print(f"# maps={maps} {op}: {json.dumps(r)}", file=sys.stderr, flush=True)
             out[f"maps{maps}_{op}"] = r
         a, b = out[f"maps{maps}_none"], out[f"maps{maps}_sum.int"]
         out[f"maps{maps}_records_per_group"] = round(b["combine_in_records"] / max(1, b["combine_groups"]), 1)
         out[f"maps{maps}_delivered_ratio"] = round(a["bytes_delivered"] / max(1, b["bytes_delivered"]), 1)
+        if shaped:
+            continue
         # kernel phases of one task's merge (last of three calls per op)
         env = dict(os.environ, UDA_GM_PROFILE="1")
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "combine_kernels", "--gb", str(args.gb),
@@ -563,6 +615,13 @@ def main() -> int:
     ap.add_argument("--validate", action="store_true")
     ap.add_argument("--budget-gb", type=float, default=10.0, help="hybrid_budget: mapred.uda.gpu.hbm.budget")
     ap.add_argument("--merge-gb", type=float, default=8.0, help="hybrid_budget: mapred.uda.gpu.merge.bytes")
+    ap.add_argument("--vocab", type=int, default=0,
+                    help="combine: words drawn uniformly from this many (default: the Zipf generator's 100 000)")
+    ap.add_argument("--tasks", type=int, default=0, help="combine: concurrent reduce tasks (default 16)")
+    ap.add_argument("--lpq", action="store_true", help="combine --over-budget: mapred.uda.gpu.hybrid.direct=0 (LPQ spills)")
+    ap.add_argument("--over-budget", action="store_true",
+                    help="combine: host MOFs under a device budget of a quarter of a task's input, "
+                         "mapred.uda.merge.combine.over.budget skip vs combine")
     a = ap.parse_args()
     fn = globals()[a.config]
     out = fn(a)

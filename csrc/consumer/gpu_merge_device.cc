@@ -807,6 +807,7 @@ bool ReduceTask::merge_gpu_device(bool probe) {
     dcv.notify_all();
   };
   DeviceMergeOut m;
+  int64_t merge_rounds = 0;
   for (int q = 0; q < rplan.rounds; ++q) {
     {
       const int64_t tw = trace::host_enabled() ? trace::now_ns() : 0;
@@ -838,12 +839,13 @@ bool ReduceTask::merge_gpu_device(bool probe) {
           push(DJob{dst, cuts, last_inner && last_outer, last_inner});
           round_closed = round_closed || last_inner;
         },
-        256ll << 20, combine_);
+        merge_round_bytes_, combine_);
     // slices holding only EOF markers: the merge saw no records and never called back, but the
     // delivery thread still has to count this round as handed over
     if (!round_closed) push(DJob{nullptr, {}, false, true});
     m.records += r.records;
     m.records_in += r.records_in;
+    merge_rounds += r.rounds;
     if (trace::host_enabled())
       trace::host_event("gr_merge", (int64_t)(uintptr_t)&ws, q,
                         trace::now_ns() - (int64_t)(std::chrono::steady_clock::now() - tq).count(), trace::now_ns());
@@ -874,6 +876,7 @@ bool ReduceTask::merge_gpu_device(bool probe) {
   ws_lease.clean = true;
   std::lock_guard<std::mutex> g(st_mu_);
   st_.records = m.records;
+  st_.merge_rounds = merge_rounds;
   if (combine_ != CombineOp::kNone) {
     st_.combine_in_records = m.records_in;
     st_.combine_groups = m.records;

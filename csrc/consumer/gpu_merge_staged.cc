@@ -157,8 +157,26 @@ class StagedMerge {
   int64_t group_raw_ = 0;
   size_t checkpointed_ = 0;
   double fetch_ms_ = 0, prog_fetch_ms_ = -1;
-  int64_t combine_in_ = 0;
+  std::atomic<int64_t> combine_in_{0};  // (the LPQ thread counts its merges' input too)
   bool combine_skipped_ = false;
+  // over budget under mapred.uda.merge.combine.over.budget=combine: the op of the RPQ rounds, and of the
+  // LPQ merges (kNone under an LPQ checkpoint: its spills stay as a resumed attempt expects them)
+  CombineOp hybrid_combine_ = CombineOp::kNone, lpq_combine_ = CombineOp::kNone;
+  // The budget counts ~3x the input per merge; a combining merge holds 17 B per record more (group index,
+  // sums: 0.27 of the input at 64 B records, as the device path's admission counts them), so its input
+  // shrinks by 3 / 3.27: an RPQ round's target of half the budget, and an LPQ group's whole budget.
+  static int64_t less_combine(int64_t b, CombineOp op) {
+    return op != CombineOp::kNone ? (int64_t)((double)b * (3.0 / 3.27)) : b;
+  }
+  int64_t round_target() const { return less_combine(budget_ / 2, hybrid_combine_); }
+  // (with direct RPQ there is no LPQ merge: the budget only decides when the task stops being an online one)
+  int64_t group_budget() const { return direct_ok_ ? budget_ : less_combine(budget_, lpq_combine_); }
+  // Sparse-index granularity of an LPQ spill. A combined spill can be far smaller than the budget, so it is
+  // sampled as finely as DirectProg samples partitions: the RPQ planner can then still cut it into rounds.
+  int64_t lpq_spacing() const {
+    if (lpq_combine_ == CombineOp::kNone) return kSampleSpacing;
+    return std::clamp<int64_t>(budget_ / 64, 4 << 10, kSampleSpacing);
+  }
   bool eof_sent_ = false;
   std::vector<uint8_t> tail_;
   hipStream_t s_ = nullptr;
@@ -229,7 +247,9 @@ void StagedMerge::run() {
     kv_ = t_.kv_buf_size_ - kEofBytes;
     lpq_wait();  // an LPQ of the fetch phase may still be merging
     // mapred.uda.merge.combine: the online and progressive merges combine; the over-budget hybrid (LPQ /
-    // RPQ rounds, progressive direct) delivers the uncombined stream, which a combiner allows
+    // RPQ rounds, progressive direct) delivers the uncombined stream, which a combiner allows, unless
+    // mapred.uda.merge.combine.over.budget=combine: then every RPQ round (and LPQ merge) combines, the host
+    // planner never splitting equal keys between rounds (rpq_plan.h)
     if (dprog_) {
       run_progressive_direct();
     } else if (progressive_) {
@@ -318,6 +338,8 @@ void StagedMerge::read_conf() {
   // LPQ checkpoint (disk tier): spills_[0, checkpointed_) are fsynced, indexed in <path>.idx and
   // listed in the manifest; a failed attempt keeps them for the next one
   ckpt_ = t_.checkpoint_ && tier_ == "disk";
+  hybrid_combine_ = t_.combine_over_budget_ ? t_.combine_ : CombineOp::kNone;
+  lpq_combine_ = ckpt_ ? CombineOp::kNone : hybrid_combine_;
   // Progressive phases (ProgFetch). Default (-1): 4 phases when the task is the only staged GPU merge on
   // its device when it decides (a lone task: 22 -> 26.3-26.8 GB/s on the 2 GB secondary sort); concurrent
   // tasks already overlap each other's H2D and D2H and gain nothing
@@ -530,7 +552,7 @@ void StagedMerge::drain_ready(const std::vector<std::shared_ptr<MofFetcher>>& re
     while (next < ready.size()) {
       const int64_t pl = std::max<int64_t>(ready[next]->part_len(), 0);
       const int64_t est = pl * (t_.codec_ != Codec::kNone ? 3 : 1);  // decoded size estimate
-      if (!direct_ && (!group_.empty() || !sub.empty()) && group_raw_ + est > budget_) break;
+      if (!direct_ && (!group_.empty() || !sub.empty()) && group_raw_ + est > group_budget()) break;
       sub.push_back(next++);
       group_raw_ += est;
     }
@@ -706,7 +728,18 @@ void StagedMerge::merge_spill(std::vector<Span> jg, std::vector<std::string> ids
   const int64_t tl = trace::host_enabled() ? trace::now_ns() : 0;
   if (st) st->flush();
   const int64_t tm = tl ? trace::now_ns() : 0;
-  DeviceMergeOut m = device_merge(ws, jg, stage_codec_, t_.kind_, kSampleSpacing, s);
+  // under lpq_combine_ the spill holds one record per key of its group (the RPQ rounds combine again:
+  // wrapping sums are associative, so the delivered bits do not depend on the grouping)
+  DeviceMergeOut m;
+  try {
+    m = device_merge(ws, jg, stage_codec_, t_.kind_, lpq_spacing(), s, nullptr, false, lpq_combine_);
+  } catch (const std::runtime_error& e) {
+    // the merge's cuts are the index samples, and a cut spacing bounds the record size: a record longer than
+    // the finer spacing of a combined spill takes the usual one
+    if (lpq_spacing() == kSampleSpacing || !std::strstr(e.what(), "record larger than the delivery buffer")) throw;
+    m = device_merge(ws, jg, stage_codec_, t_.kind_, kSampleSpacing, s, nullptr, false, lpq_combine_);
+  }
+  if (lpq_combine_ != CombineOp::kNone) combine_in_ += m.records_in;
   if (tl) {
     trace::host_event("lpq_flush", (int64_t)jg.size(), 0, tl, tm);
     trace::host_event("lpq_merge", m.bytes, (int64_t)jg.size(), tm, trace::now_ns());
@@ -833,6 +866,10 @@ gpu::GenericMerger::RoundFn StagedMerge::round_sink(bool last_phase) {
     DeviceMergeOut r;
     r.cuts = cuts;
     r.records = records;
+    {
+      std::lock_guard<std::mutex> g(t_.st_mu_);
+      t_.st_.merge_rounds++;
+    }
     deliver(r, last && last_phase, ws_->copy_stream(), *ws_);
   };
 }
@@ -911,14 +948,14 @@ bool StagedMerge::plan_more(DirectPlan& pl, bool wait) {
 }
 
 void StagedMerge::run_progressive_direct() {
-  combine_skipped_ = t_.combine_ != CombineOp::kNone;
+  combine_skipped_ = t_.combine_ != CombineOp::kNone && hybrid_combine_ == CombineOp::kNone;
   DirectProg& dp = *dprog_;
   const int K = dp.K;
   DirectPlan pl;
   pl.runs.resize((size_t)K);
   pl.at.assign((size_t)K, 0);
   pl.taken.assign((size_t)K, 0);
-  pl.target = std::max<int64_t>(budget_ / 2, dp.spacing);
+  pl.target = std::max<int64_t>(round_target(), dp.spacing);
   // three workspaces, two rounds prepared ahead (as the direct RPQ of run_hybrid)
   RpqPipeline pipe;
   open_pipeline(&pipe);
@@ -928,7 +965,8 @@ void StagedMerge::run_progressive_direct() {
     std::vector<Span> views((size_t)K);
     for (int k = 0; k < K; ++k)
       views[(size_t)k] = Span{mems[(size_t)k] + rr[(size_t)k].first, rr[(size_t)k].second - rr[(size_t)k].first};
-    return device_merge(*pipe.ws[q % 3], views, Codec::kNone, t_.kind_, kv_, pipe.s[q % 3], nullptr, true);
+    return device_merge(*pipe.ws[q % 3], views, Codec::kNone, t_.kind_, kv_, pipe.s[q % 3], nullptr, true,
+                        hybrid_combine_);
   };
   std::vector<std::future<DeviceMergeOut>> next;
   // at most three rounds in flight (one delivering, two preparing): workspace q % 3 is free again
@@ -951,6 +989,7 @@ void StagedMerge::run_progressive_direct() {
     issue(q);
     if (q >= pl.rounds.size()) continue;
     DeviceMergeOut m = next[q].get();
+    if (hybrid_combine_ != CombineOp::kNone) combine_in_ += m.records_in;
     issue(q);
     deliver(m, pl.planned_all && q + 1 == pl.rounds.size(), pipe.s[q % 3], *pipe.ws[q % 3]);
     ++q;
@@ -1016,7 +1055,8 @@ void StagedMerge::run_progressive() {
                                 pf.dev[(size_t)k] + start[(size_t)k]};
     }
     const DeviceMergeOut pm =
-        device_merge(ws, spans, Codec::kNone, t_.kind_, kv_, s_, round_sink(last_phase), false, t_.combine_);
+        device_merge(ws, spans, Codec::kNone, t_.kind_, kv_, s_, round_sink(last_phase), false, t_.combine_,
+                     t_.merge_round_bytes_);
     combine_in_ += pm.records_in;
   }
   for (auto& t : pf.threads) t.join();
@@ -1030,7 +1070,8 @@ void StagedMerge::run_online() {
     stager_->flush();
     ws_->h2d_ms += ms_since(tf);
   }
-  DeviceMergeOut m = device_merge(*ws_, group_, stage_codec_, t_.kind_, kv_, s_, round_sink(true), false, t_.combine_);
+  DeviceMergeOut m = device_merge(*ws_, group_, stage_codec_, t_.kind_, kv_, s_, round_sink(true), false, t_.combine_,
+                                  t_.merge_round_bytes_);
   combine_in_ += m.records_in;
   count_decoded(m.decoded_blocks);
 }
@@ -1087,7 +1128,7 @@ std::vector<std::vector<int64_t>> StagedMerge::run_bounds(const std::vector<std:
 
 // hybrid: last LPQ, then RPQ rounds over the spilled runs (direct: over the partitions)
 void StagedMerge::run_hybrid() {
-  combine_skipped_ = t_.combine_ != CombineOp::kNone;
+  combine_skipped_ = t_.combine_ != CombineOp::kNone && hybrid_combine_ == CombineOp::kNone;
   if (direct_) {
     spills_ = direct_head_.get();
     for (auto& r : direct_runs_) spills_.push_back(std::move(r));
@@ -1099,8 +1140,20 @@ void StagedMerge::run_hybrid() {
   // splitters every ~budget/2 bytes of input (a sample stands for the bytes up to its run's next cut)
   std::vector<int64_t> at((size_t)R, 0), end((size_t)R);
   for (int r = 0; r < R; ++r) end[(size_t)r] = spills_[(size_t)r].bytes;
-  const std::vector<std::string> split =
-      plan_splitters(spills_, at, end, std::max<int64_t>(budget_ / 2, kSampleSpacing), t_.kind_);
+  int64_t target = std::max<int64_t>(round_target(), kSampleSpacing);
+  if (!direct_ && lpq_combine_ != CombineOp::kNone) {
+    // Combined spills can all fit one round of the budget. They are still planned in at least two key-range
+    // rounds, so an over-budget task runs the RPQ the way uncombined spills (always larger than the budget)
+    // make it run: several combining rounds through the pipeline. Measured (docs/BENCHMARKS.md), the extra
+    // round does not pay for itself up to 100 MB of spills: it costs the launches and synchronizes of one
+    // more device merge, so the minimum is two and not the pipeline's three workspaces.
+    int64_t tot = 0;
+    for (int r = 0; r < R; ++r) tot += end[(size_t)r];
+    const char* mr = std::getenv("UDA_RPQ_MIN_ROUNDS");  // A/B: 1 plans them by the budget alone
+    const int64_t min_rounds = mr && *mr ? std::max<int64_t>(1, std::atoll(mr)) : 2;
+    target = std::min(target, std::max<int64_t>(lpq_spacing(), (tot + min_rounds - 1) / min_rounds));
+  }
+  const std::vector<std::string> split = plan_splitters(spills_, at, end, target, t_.kind_);
   const std::vector<RoundSlices> slices = slice_rounds(run_bounds(split), at, end, false, false);
   const int rounds = (int)split.size() + 1;
   {
@@ -1129,12 +1182,16 @@ void StagedMerge::run_hybrid() {
       }
     }
     // views: pinned host spans (spill arena or slice arena): SDMA H2D, not a blit kernel
-    return device_merge(*pipe.ws[q % 3], views, Codec::kNone, t_.kind_, kv_, pipe.s[q % 3], nullptr, true);
+    return device_merge(*pipe.ws[q % 3], views, Codec::kNone, t_.kind_, kv_, pipe.s[q % 3], nullptr, true,
+                        hybrid_combine_);
   };
   std::vector<std::future<DeviceMergeOut>> next((size_t)rounds);
   for (int q = 0; q < std::min(rounds, 2); ++q) next[(size_t)q] = std::async(std::launch::async, prep, q);
   for (int q = 0; q < rounds; ++q) {
     DeviceMergeOut m = next[(size_t)q].get();
+    // records enter a combining merge once: at the LPQ level when it combines, else here
+    if (hybrid_combine_ != CombineOp::kNone && (direct_ || lpq_combine_ == CombineOp::kNone))
+      combine_in_ += m.records_in;
     // workspace (q + 2) % 3 delivered round q - 1 before this iteration
     if (q + 2 < rounds) next[(size_t)q + 2] = std::async(std::launch::async, prep, q + 2);
     const int64_t td = trace::host_enabled() ? trace::now_ns() : 0;

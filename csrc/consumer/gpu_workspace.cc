@@ -38,7 +38,7 @@ std::atomic<int>& staged_merges(int device) {
 
 DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_runs, Codec codec, KeyKind kind,
                             int64_t spacing, hipStream_t s, const gpu::GenericMerger::RoundFn& on_round,
-                            bool pinned_src, CombineOp combine) {
+                            bool pinned_src, CombineOp combine, int64_t round_bytes) {
   double round_ms = 0;
   gpu::GenericMerger::RoundFn timed;
   if (on_round)
@@ -67,7 +67,7 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
     auto t1 = std::chrono::steady_clock::now();
     ws.h2d_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
     gpu::GenericMergeResult r =
-        ws.merger.merge(runs, lens, (int)kind, ws.out.as<uint8_t>(), total, spacing, s, timed, 256ll << 20, combine);
+        ws.merger.merge(runs, lens, (int)kind, ws.out.as<uint8_t>(), total, spacing, s, timed, round_bytes, combine);
     HIP_CHECK(hipStreamSynchronize(s));
     ws.device_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count() - round_ms;
     DeviceMergeOut res;
@@ -154,7 +154,7 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
   }
   host_raw.clear();
   gpu::GenericMergeResult r =
-      ws.merger.merge(runs, bytes, (int)kind, out.as<uint8_t>(), total, spacing, s, timed, 256ll << 20, combine);
+      ws.merger.merge(runs, bytes, (int)kind, out.as<uint8_t>(), total, spacing, s, timed, round_bytes, combine);
   HIP_CHECK(hipStreamSynchronize(s));
   ws.device_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count() - round_ms;
   if (tm) trace::host_event("dm_merge", total, (int64_t)ptrs.size(), tm, trace::now_ns());

@@ -536,7 +536,8 @@ struct GateLease {
 // delivery engine) instead of a blit kernel whose host reads would slow the merge kernels beside it.
 DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_runs, Codec codec, KeyKind kind,
                             int64_t spacing, hipStream_t s, const gpu::GenericMerger::RoundFn& on_round = nullptr,
-                            bool pinned_src = false, CombineOp combine = CombineOp::kNone);
+                            bool pinned_src = false, CombineOp combine = CombineOp::kNone,
+                            int64_t round_bytes = 256ll << 20);  // on_round's rounds (mapred.uda.gpu.merge.round.bytes)
 
 // piece boundaries (in cut indices) of a merged output: pieces of up to `limit` bytes ending on record
 // boundaries; empty if a single cut interval is larger than `limit`

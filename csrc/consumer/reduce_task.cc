@@ -451,6 +451,13 @@ void ReduceTask::on_init(const InitParams& p_in) {
   const std::string comb = host_->get_conf("mapred.uda.merge.combine", "none");
   if (!combine_op_from_conf(comb, &combine_))
     throw ProtocolError("unknown mapred.uda.merge.combine \"" + comb + "\" (" + kCombineAllowed + ")");
+  // the over-budget GPU hybrid (LPQ spills, RPQ rounds) delivers the uncombined stream unless told to combine
+  const std::string cob = host_->get_conf("mapred.uda.merge.combine.over.budget", "skip");
+  if (cob != "skip" && cob != "combine")
+    throw ProtocolError("unknown mapred.uda.merge.combine.over.budget \"" + cob + "\" (skip or combine)");
+  combine_over_budget_ = cob == "combine";
+  // key-range rounds in which one device merge hands its output over (GenericMerger::merge's round_bytes)
+  merge_round_bytes_ = std::max<int64_t>(4 << 10, host_->conf_i64("mapred.uda.gpu.merge.round.bytes", 256ll << 20));
   if (backend_ == "gpu") {
     // FIXED10 delivery: bit-packed D2H pieces (gpu/fixed_delivery.h) and the D2H granule
     const std::string pack = host_->get_conf("mapred.uda.gpu.delivery.pack", "auto");
@@ -998,7 +1005,7 @@ std::string ReduceTask::stats_json() const {
     << ",\"host_fetched_bytes\":" << s.host_fetched_bytes << ",\"local_read_bytes\":" << s.local_read_bytes << ",\"hbm_wait_ms\":" << s.hbm_wait_ms
     << ",\"hbm_reserved\":" << s.hbm_reserved << ",\"round_bytes\":" << s.round_bytes << ",\"gpu_device\":" << s.gpu_device << ",\"merge_path\":\"" << s.merge_path << "\""
     << ",\"combine\":\"" << s.combine << "\",\"combine_in_records\":" << s.combine_in_records
-    << ",\"combine_groups\":" << s.combine_groups
+    << ",\"combine_groups\":" << s.combine_groups << ",\"merge_rounds\":" << s.merge_rounds
     << ",\"finished\":" << (finished_ ? "true" : "false") << "}";
   return o.str();
 }

@@ -97,6 +97,7 @@ struct ReduceStats {
   // it delivered. records / bytes_delivered / buffers count what was delivered.
   std::string combine = "none";
   int64_t combine_in_records = 0, combine_groups = 0;
+  int64_t merge_rounds = 0;     // GPU: hand-overs of device merges' output (rounds of mapred.uda.gpu.merge.round.bytes)
   std::string backend;
 };
 
@@ -206,6 +207,8 @@ class ReduceTask {
   double hbm_budget_conf_ = 0;
   int delivery_pack_ = 2;                       // mapred.uda.gpu.delivery.pack: colpack version, 0 = off
   CombineOp combine_ = CombineOp::kNone;        // mapred.uda.merge.combine
+  bool combine_over_budget_ = false;            // mapred.uda.merge.combine.over.budget = combine (default skip)
+  int64_t merge_round_bytes_ = 256ll << 20;     // mapred.uda.gpu.merge.round.bytes: a device merge's hand-over rounds
   int64_t delivery_piece_bytes_ = 64ll << 20;   // mapred.uda.gpu.delivery.piece.bytes
   int device_ = 0;
   int registry_slot_ = -1;

@@ -9,6 +9,12 @@
 //   (exclusive scan of sizes: output offsets; a non-head shares the offset of the next head)
 //   gather_combine_kernel   copies the head records, their last W bytes replaced by the big-endian sum
 //
+// Streamed key-range rounds (a merge of more than round_bytes) run the same three on the subrange a round
+// delivers; two more kernels serve them:
+//   combine_check_values_kernel  any value not W bytes long, over all records, before F3
+//   combine_round_heads_kernel   head flags of the elements a round added, and the round close: the
+//                                highest head position, where the still open last group begins
+//
 // Sums are unsigned 64-bit integers (the low 32 bits serve sum.int): wrapping adds are associative, so
 // the result is the same bits in any reduction order, atomics included.
 #include "generic_cmp.h"
@@ -54,6 +60,41 @@ __global__ void __launch_bounds__(256) combine_heads_kernel(GenericKeyCtx ctx, c
   heads[i] = (i == 0 || !same_key(ctx, order[i - 1], e)) ? 1 : 0;
   // error path only: the lowest merged position with a value the op cannot sum
   if (value_bytes(ctx, e.lo & kGenOrdMask) != W) atomicMin(bad, (unsigned long long)i);
+}
+
+// Streamed rounds (generic_merger.cc): the value-length check over every record of the side tables, in
+// record order. It runs before F3 and says only whether any value is not W bytes long; the whole path
+// then finds the lowest merged position for the error.
+__global__ void __launch_bounds__(256) combine_check_values_kernel(GenericKeyCtx ctx, int64_t n, int W, int* any_bad) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool bad = g < n && value_bytes(ctx, (uint64_t)g) != W;
+  if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(any_bad, 1);
+}
+
+// Streamed rounds: the head flags of the merged elements [i0, i1) a round added (element i0 compares with
+// i0 - 1, which an earlier round merged), and the round close: *last_head = 1 + the highest head position
+// in the range (0 stays for none), a max over each wave, then over the workgroup's waves in LDS, then one
+// atomicMax per workgroup that saw a head.
+__global__ void __launch_bounds__(256) combine_round_heads_kernel(GenericKeyCtx ctx, const Elem* order, int64_t i0,
+                                                                  int64_t i1, int64_t* heads,
+                                                                  unsigned long long* last_head) {
+  __shared__ unsigned long long wmax[4];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int64_t i = i0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned long long m = 0;
+  if (i < i1) {
+    const bool h = i == 0 || !same_key(ctx, order[i - 1], order[i]);
+    heads[i] = h ? 1 : 0;
+    if (h) m = (unsigned long long)i + 1;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) m = max(m, (unsigned long long)__shfl_xor(m, off, 64));
+  if (lane == 0) wmax[wid] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    m = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+    if (m != 0) atomicMax(last_head, m);
+  }
 }
 
 // One merged element per lane, kCombineTile per workgroup. A wave's values are summed by a segmented
@@ -207,6 +248,20 @@ void launch_combine_heads(GenericKeyCtx ctx, const Elem* order, int64_t n, int W
   if (n <= 0) return;
   hipLaunchKernelGGL(combine_heads_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ctx, order, n, W,
                      heads, bad);
+}
+
+void launch_combine_check_values(GenericKeyCtx ctx, int64_t n, int W, int* any_bad, hipStream_t s) {
+  (void)hipMemsetAsync(any_bad, 0, sizeof(int), s);
+  if (n <= 0) return;
+  hipLaunchKernelGGL(combine_check_values_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ctx, n, W,
+                     any_bad);
+}
+
+void launch_combine_round_heads(GenericKeyCtx ctx, const Elem* order, int64_t i0, int64_t i1, int64_t* heads,
+                                unsigned long long* last_head, hipStream_t s) {
+  if (i1 <= i0) return;
+  hipLaunchKernelGGL(combine_round_heads_kernel, dim3((unsigned)((i1 - i0 + 255) / 256)), dim3(256), 0, s, ctx, order,
+                     i0, i1, heads, last_head);
 }
 
 void launch_combine_sums(GenericKeyCtx ctx, const Elem* order, const int64_t* gidx, int64_t n, int W,

@@ -360,10 +360,130 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
     if (cuts_host_.size() < (size_t)entries * 8) cuts_host_.alloc((size_t)entries * 8 + 4096);
   };
   int64_t C = 0;
-  // (not under combine: a streamed round's bytes rb[q] come from input sizes, and a group of equal keys can
-  // straddle two cells, the order's tie-break being the ordinal)
-  if (combine == CombineOp::kNone && gk && on_round &&
-      kway_level(0, cur, eoff, d_eoff, d_eoff, nxt, ctx, s, /*launch_cells=*/false, &C)) {
+  const int64_t want_rounds = (bytes + std::max<int64_t>(round_bytes, 1) - 1) / std::max<int64_t>(round_bytes, 1);
+  // Under combine a merge of more than round_bytes is streamed in rounds that end on group boundaries
+  // (below), unless a value has the wrong length: the whole path then reports it before anything is written.
+  bool stream_combine = false;
+  if (combine != CombineOp::kNone && gk && on_round && want_rounds > 1) {
+    reserve_combine(total);
+    int* d_any = reinterpret_cast<int*>(cflag_.as<uint8_t>() + 8);
+    launch_combine_check_values(ctx, total, combine_value_bytes(combine), d_any, s);
+    int any = 0;
+    HIP_CHECK(hipMemcpyAsync(&any, d_any, 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    stream_combine = any == 0;
+    phase("f4c_check_values");
+  }
+  if (stream_combine && kway_level(0, cur, eoff, d_eoff, d_eoff, nxt, ctx, s, /*launch_cells=*/false, &C)) {
+    // ---- streamed under combine: key-range rounds of cells as below, but a group of equal keys can
+    // straddle two cells (the order's tie-break is the ordinal), so a round delivers the groups that are
+    // closed, [a, hold), where hold is the last head the merged order has so far, and carries the open
+    // group [hold, re[q + 1]) into the next round. The carried elements' heads stay in sizes_ (1 at hold,
+    // then zeros): every element gets its head flag once, and is scanned, summed and gathered once, in the
+    // round that delivers it. A group longer than a round delivers nothing until it closes.
+    res.passes = 1;
+    res.records = 0;
+    const int W = combine_value_bytes(combine);
+    const int64_t chunk = chunk_bytes(cur);
+    const int Q = (int)std::min<int64_t>(C, want_rounds);
+    std::vector<int64_t> cb(Q + 1);
+    for (int q = 0; q <= Q; ++q) cb[q] = C * q / Q;
+    if (rounds_.size() < (size_t)(Q + 1) * 32) rounds_.alloc((size_t)(Q + 1) * 32);
+    int64_t* d_cb = rounds_.as<int64_t>();
+    int64_t* d_re = d_cb + (Q + 1);
+    int64_t* d_rb = d_re + (Q + 1);
+    auto* d_hold = reinterpret_cast<unsigned long long*>(d_rb + (Q + 1));  // per round: 1 + its last head
+    HIP_CHECK(hipMemcpyAsync(d_cb, cb.data(), 8 * (Q + 1), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemsetAsync(d_hold, 0, 8 * (size_t)Q, s));
+    launch_gk_round_bounds(gk_[0].split.as<int64_t>(), K, C, d_cb, Q + 1,
+                           const_cast<const int64_t* const*>(d_offp), d_re, d_rb, s);
+    std::vector<int64_t> re(Q + 1), rb(Q + 1);
+    HIP_CHECK(hipMemcpyAsync(re.data(), d_re, 8 * (Q + 1), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(rb.data(), d_rb, 8 * (Q + 1), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemsetAsync(gk_[0].flag.as(), 0, 4, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    // A round writes at most the records its cells added and the head of the group carried into it: its
+    // cuts are sized from rb with one delivery buffer of slack (the compacted size is read with the cuts).
+    // Pinned host state per round, after the cuts: last head + 1, cell overflow, groups, bytes.
+    std::vector<int64_t> coff(Q + 1, 0), nbuf(Q), cnt(Q, 0);
+    for (int q = 0; q < Q; ++q) {
+      nbuf[q] = (rb[q + 1] - rb[q] + kv_buf + chunk - 1) / chunk;
+      coff[q + 1] = coff[q] + nbuf[q] + 1;
+    }
+    reserve_cuts(coff[Q] + 4 * (int64_t)Q);
+    int64_t* h_state = cuts_host_.as<int64_t>() + coff[Q];
+    std::fill(h_state, h_state + 4 * (int64_t)Q, 0);
+    for (int q = (int)round_ev_.size(); q < 2 * Q; ++q) {  // per round: cells and heads done, F4 done
+      hipEvent_t e;
+      HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      round_ev_.push_back(e);
+    }
+    int64_t* d_heads = sizes_.as<int64_t>();
+    int64_t* d_gidx = gidx_.as<int64_t>();
+    int64_t* d_off = out_off_.as<int64_t>();
+    auto* d_sums = sums_.as<unsigned long long>();
+    auto enqueue_cells = [&](int q) {
+      launch_gk_cells(ctx, cur, d_eoff, K, gk_[0].split.as<int64_t>(), C, cb[q], cb[q + 1] - cb[q], nxt,
+                      gk_[0].flag.as<int>(), s);
+      launch_combine_round_heads(ctx, nxt, re[q], re[q + 1], d_heads, d_hold + q, s);
+      HIP_CHECK(hipMemcpyAsync(h_state + 4 * q, d_hold + q, 8, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(h_state + 4 * q + 1, gk_[0].flag.as(), 4, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipEventRecord(round_ev_[(size_t)(2 * q)], s));
+    };
+    int64_t a = 0, B = 0;  // first merged element, and output byte, not yet delivered
+    // Round q's cells are merged: where it ends, and the F4 of what it delivers (elements [a, a + cnt[q]),
+    // workspace slices from a, output from B). Needs the earlier rounds' bytes, so it runs after their F4.
+    auto close_round = [&](int q) {
+      HIP_CHECK(hipEventSynchronize(round_ev_[(size_t)(2 * q)]));
+      if (h_state[4 * q + 1]) throw std::runtime_error("generic k-way: a cell above capacity in a streamed round");
+      const bool last = q + 1 == Q;
+      const int64_t hold = std::max(a, h_state[4 * q] - 1);
+      const int64_t end = last ? total : hold;
+      if (!last) res.held_records += re[q + 1] - hold;
+      const int64_t n = end - a;
+      cnt[q] = n;
+      if (n == 0) return;  // one open group from a on: carried whole
+      launch_exclusive_scan(d_heads + a, d_gidx + a, n, scan_tmp_.as<int64_t>(), s);
+      launch_combine_sums(ctx, nxt + a, d_gidx + a, n, W, d_sums + a, d_heads + a, s);
+      launch_exclusive_scan(d_heads + a, d_off + a, n, scan_tmp_.as<int64_t>(), s);
+      launch_gather_combine(ctx, nxt + a, n, d_gidx + a, d_off + a, d_sums + a, W, out + B, s);
+      launch_buffer_cuts(d_off + a, n, chunk, nbuf[q], cuts_.as<int64_t>() + coff[q], s);
+      HIP_CHECK(hipMemcpyAsync(cuts_host_.as<int64_t>() + coff[q], cuts_.as<int64_t>() + coff[q], 8 * (nbuf[q] + 1),
+                               hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(h_state + 4 * q + 2, d_gidx + a + n, 8, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(h_state + 4 * q + 3, d_off + a + n, 8, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipEventRecord(round_ev_[(size_t)(2 * q + 1)], s));
+      a = end;
+    };
+    res.cuts = {0};
+    std::vector<int64_t> rc;
+    enqueue_cells(0);
+    if (Q > 1) enqueue_cells(1);
+    close_round(0);
+    for (int q = 0; q < Q; ++q) {
+      // the device runs ahead while round q is delivered: the cells of round q + 2, then round q + 1's F4
+      if (q + 2 < Q) enqueue_cells(q + 2);
+      int64_t groups = 0;
+      if (cnt[q] > 0) {
+        HIP_CHECK(hipEventSynchronize(round_ev_[(size_t)(2 * q + 1)]));
+        groups = h_state[4 * q + 2];
+        const int64_t cbytes = h_state[4 * q + 3];
+        absolute_cuts(cuts_host_.as<int64_t>() + coff[q], nbuf[q], B, cbytes, &rc);
+        B += cbytes;
+        res.records += groups;
+      }
+      if (q + 1 < Q) close_round(q + 1);
+      if (cnt[q] > 0) {
+        on_round(rc, groups, q + 1 == Q);
+        ++res.rounds;
+        res.cuts.insert(res.cuts.end(), rc.begin() + 1, rc.end());
+      }
+    }
+    res.bytes = B;
+    HIP_CHECK(hipStreamSynchronize(s));
+    phase("f3_f4c_rounds");
+  } else if (combine == CombineOp::kNone && gk && on_round &&
+             kway_level(0, cur, eoff, d_eoff, d_eoff, nxt, ctx, s, /*launch_cells=*/false, &C)) {
     // ---- streamed: key-range rounds of cells; round q's output is handed over (on_round) while the
     // device merges round q + 1, so the caller's D2H overlaps the merge
     res.passes = 1;
@@ -412,6 +532,7 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
       if (overflow) throw std::runtime_error("generic k-way: a cell above capacity in a streamed round");
       absolute_cuts(cuts_host_.as<int64_t>() + coff[q], nbufs[q], rb[q], rb[q + 1] - rb[q], &rc);
       on_round(rc, re[q + 1] - re[q], q + 1 == Q);
+      ++res.rounds;
       res.cuts.insert(res.cuts.end(), rc.begin() + 1, rc.end());
     }
     HIP_CHECK(hipStreamSynchronize(s));
@@ -487,7 +608,10 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
       HIP_CHECK(hipMemcpyAsync(cuts_host_.as<int64_t>(), cuts_.as<int64_t>(), 8 * (nbuf + 1), hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
       absolute_cuts(cuts_host_.as<int64_t>(), nbuf, 0, cbytes, &res.cuts);
-      if (on_round) on_round(res.cuts, groups, true);
+      if (on_round) {
+        on_round(res.cuts, groups, true);
+        ++res.rounds;
+      }
     } else {
       const int64_t nbuf = (bytes + chunk - 1) / chunk;
       reserve_cuts(nbuf + 1);
@@ -495,7 +619,10 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
       f4_enqueue(cur, 0, total, 0, bytes, chunk, cuts_.as<int64_t>(), cuts_host_.as<int64_t>(), /*timed=*/true);
       HIP_CHECK(hipStreamSynchronize(s));
       absolute_cuts(cuts_host_.as<int64_t>(), nbuf, 0, bytes, &res.cuts);
-      if (on_round) on_round(res.cuts, total, true);
+      if (on_round) {
+        on_round(res.cuts, total, true);
+        ++res.rounds;
+      }
     }
   }
   phase("f4_gather_cuts");

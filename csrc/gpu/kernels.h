@@ -227,6 +227,13 @@ constexpr int kCombineTile = 256;  // merged elements per workgroup of launch_co
 // *bad = lowest i whose record's value is not W bytes long, ~0 if none (set here).
 void launch_combine_heads(GenericKeyCtx ctx, const Elem* order, int64_t n, int W, int64_t* heads,
                           unsigned long long* bad, hipStream_t s);
+// Streamed rounds. *any_bad = 1 if any of the n records of the side tables has a value that is not W bytes
+// long, else 0 (set here); independent of the merged order, so it runs before F3.
+void launch_combine_check_values(GenericKeyCtx ctx, int64_t n, int W, int* any_bad, hipStream_t s);
+// heads[i] for the merged elements i in [i0, i1) (i0 > 0 compares with element i0 - 1), and the round
+// close: *last_head = max(*last_head, 1 + the highest head position in [i0, i1)); the caller zeroes it.
+void launch_combine_round_heads(GenericKeyCtx ctx, const Elem* order, int64_t i0, int64_t i1, int64_t* heads,
+                                unsigned long long* last_head, hipStream_t s);
 // gidx = exclusive scan of heads (n + 1 entries). sums[q] = sum of the values of group q modulo 2^64
 // (n entries of room, zeroed here; values of records flagged in *bad count as 0), and the F4 sizes
 // under combine: sizes[i] = record size of a head, 0 for any other element.

@@ -1528,6 +1528,78 @@ PYBIND11_MODULE(_uda_native, m) {
     return py::make_tuple(out, cuts, records, passes, merge_ms, serial_runs, records_in);
   }, py::arg("runs"), py::arg("key_class"), py::arg("kv_buf") = 1 << 20, py::arg("device") = 0,
         py::arg("combine") = "none");
+  // The same merge handed over in key-range rounds of about round_bytes (GenericMerger::merge's on_round,
+  // recorded here). Returns (merged bytes, cuts, records, records merged, rounds, held records), rounds a
+  // list of (records, absolute cuts) per on_round call. gpu_merge_streamed_last_rounds(): the on_round
+  // calls of the most recent call, also of one that raised.
+  static std::atomic<int> streamed_last_rounds{0};
+  m.def("gpu_merge_streamed_last_rounds", [] { return streamed_last_rounds.load(); });
+  m.def("gpu_merge_runs_streamed", [](const py::list& runs, const std::string& key_class, int64_t kv_buf,
+                                      int64_t round_bytes, int device, const std::string& combine) {
+    KeyKind kind = key_kind_from_class(key_class.c_str());
+    if (kind == KeyKind::kUnsupported) throw py::value_error("unsupported key class");
+    if (round_bytes <= 0) throw py::value_error("round_bytes must be positive");
+    const CombineOp cop = combine_op_arg(combine);
+    std::vector<py::buffer_info> views;
+    std::vector<const uint8_t*> host;
+    std::vector<int64_t> bytes;
+    int64_t total = 0;
+    for (auto h : runs) {
+      views.push_back(py::reinterpret_borrow<py::buffer>(h).request());
+      host.push_back(static_cast<const uint8_t*>(views.back().ptr));
+      bytes.push_back((int64_t)(views.back().size * views.back().itemsize));
+      total += bytes.back();
+    }
+    gpu::GenericMergeResult res;
+    std::vector<std::pair<int64_t, std::vector<int64_t>>> calls;
+    std::vector<uint8_t> merged;
+    streamed_last_rounds = 0;
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      gpu::DeviceBuffer in, dout;
+      in.alloc((size_t)std::max<int64_t>(total, 16));
+      dout.alloc((size_t)std::max<int64_t>(total, 16));
+      gpu::GenericMerger gm;  // before the stream: its workspace outlives whatever a failed merge left queued
+      hipStream_t s = nullptr;
+      struct StreamDrop {
+        hipStream_t& s;
+        ~StreamDrop() {
+          if (s) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamDestroy(s);
+          }
+        }
+      } stream_drop{s};
+      HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      std::vector<const uint8_t*> ptrs;
+      int64_t off = 0;
+      for (size_t i = 0; i < host.size(); ++i) {
+        if (bytes[i]) HIP_CHECK(hipMemcpyAsync(in.as<uint8_t>() + off, host[i], (size_t)bytes[i], hipMemcpyHostToDevice, s));
+        ptrs.push_back(in.as<uint8_t>() + off);
+        off += bytes[i];
+      }
+      HIP_CHECK(hipStreamSynchronize(s));
+      bool closed = false;
+      res = gm.merge(ptrs, bytes, (int)kind, dout.as<uint8_t>(), total, kv_buf, s,
+                     [&](const std::vector<int64_t>& cuts, int64_t records, bool last) {
+                       if (closed) throw std::runtime_error("on_round after the last round");
+                       closed = last;
+                       calls.emplace_back(records, cuts);
+                       ++streamed_last_rounds;
+                     },
+                     round_bytes, cop);
+      HIP_CHECK(hipStreamSynchronize(s));
+      if (!calls.empty() && !closed) throw std::runtime_error("the final on_round call did not say last");
+      merged.resize((size_t)res.bytes);
+      if (res.bytes) HIP_CHECK(hipMemcpy(merged.data(), dout.as(), (size_t)res.bytes, hipMemcpyDeviceToHost));
+    }
+    py::list rounds;
+    for (auto& c : calls) rounds.append(py::make_tuple(c.first, c.second));
+    return py::make_tuple(py::bytes(reinterpret_cast<const char*>(merged.data()), merged.size()), res.cuts, res.records,
+                          res.records_in, rounds, res.held_records);
+  }, py::arg("runs"), py::arg("key_class"), py::arg("kv_buf"), py::arg("round_bytes"), py::arg("device") = 0,
+        py::arg("combine") = "none");
   // F8: sort TeraSort records (104-byte IFile records, no EOF marker) by their 10-byte key on the
   // device; returns (sorted bytes, device ms of the sort).
   m.def("gpu_sort_fixed", [](py::buffer b, int device, bool staged) {

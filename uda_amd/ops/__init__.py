@@ -40,6 +40,20 @@ def merge_runs(runs: list[bytes], key_class: str, device: str = "gpu", kv_buf: i
     raise ValueError(f"unknown device {device!r}")
 
 
+def merge_runs_streamed(runs: list[bytes], key_class: str, kv_buf: int = 1 << 20, round_bytes: int = 256 << 20,
+                        gpu_index: int = 0, combine: str = "none"):
+    """The device merge handed over in key-range rounds of about round_bytes of input, as a reduce task
+    receives it. Returns (merged record bytes, cuts, stats): stats has records, records_in, held_records and
+    rounds, a list of (records, cuts of that round) per hand-over. Under combine a round ends on a group
+    boundary: an open last group is carried into the next round (held_records counts those elements)."""
+    n = native()
+    if n.device_count() <= 0:
+        raise RuntimeError("merge_runs_streamed: no HIP device visible")
+    merged, cuts, records, records_in, rounds, held = n.gpu_merge_runs_streamed(
+        list(runs), key_class, kv_buf - 2, round_bytes, gpu_index, combine)
+    return merged, cuts, dict(records=records, records_in=records_in, rounds=rounds, held_records=held)
+
+
 def buffers(merged: bytes, cuts: list[int]) -> list[bytes]:
     """Split a merged stream at the cut offsets into delivery buffers, EOF in the last one."""
     out = [merged[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
