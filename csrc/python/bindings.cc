@@ -602,6 +602,76 @@ PYBIND11_MODULE(_uda_native, m) {
     return py::make_tuple(bufs, d);
   }, py::arg("runs"), py::arg("kv_buf"), py::arg("round_bytes"), py::arg("piece_bytes") = 64ll << 20,
      py::arg("pack") = "auto", py::arg("device") = 0);
+  // Merge given sorted FIXED10 runs (whole 104-byte records, no EOF marker) with a DeviceMerger made for
+  // this call, so the UDA_KWAY* environment of the moment applies. The runs share one device buffer; each
+  // starts at a multiple of 16 bytes plus `pad` (8: the staged kernel's half-chunk offset; 2: the
+  // alignment of Hadoop MOF partitions). Returns (merged bytes, {passes, overflow_cells, bad_layout, kway}).
+  m.def("gpu_merge_fixed", [](const py::list& runs, const py::object& group_first, int device, int pad) {
+    if (pad != 0 && pad != 8 && pad != 2) throw py::value_error("gpu_merge_fixed: pad is 0, 8 or 2");
+    const int K = (int)runs.size();
+    std::vector<std::string> host((size_t)K);
+    std::vector<size_t> at((size_t)K);
+    size_t in_bytes = 0;
+    int64_t total = 0;
+    for (int i = 0; i < K; ++i) {
+      py::buffer_info v = py::cast<py::buffer>(runs[i]).request();
+      host[i].assign((const char*)v.ptr, (size_t)(v.size * v.itemsize));
+      if (host[i].size() % (size_t)gpu::kTeraRecordBytes) throw py::value_error("gpu_merge_fixed: need whole records");
+      at[i] = ((in_bytes + 15) & ~(size_t)15) + (size_t)pad;
+      in_bytes = at[i] + host[i].size();
+      total += (int64_t)(host[i].size() / (size_t)gpu::kTeraRecordBytes);
+    }
+    std::vector<int> gf = group_first.is_none() ? std::vector<int>{0, K} : group_first.cast<std::vector<int>>();
+    for (size_t g = 0; g + 1 < gf.size(); ++g)
+      if (gf[g] > gf[g + 1]) throw py::value_error("gpu_merge_fixed: group_first must not decrease");
+    const int64_t out_bytes = total * gpu::kTeraRecordBytes;
+    PyObject* o = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)out_bytes);
+    if (!o) throw py::error_already_set();
+    py::bytes out = py::reinterpret_steal<py::bytes>(o);
+    int passes = 0, overflow = 0;
+    bool bad = false, kway = false;
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      gpu::DeviceBuffer in, merged;
+      in.alloc(std::max<size_t>(in_bytes, 16));
+      merged.alloc((size_t)std::max<int64_t>(out_bytes, 16));
+      std::vector<gpu::RunDesc> rd((size_t)K);
+      for (int i = 0; i < K; ++i) {
+        if (!host[i].empty())
+          HIP_CHECK(hipMemcpy(in.as<uint8_t>() + at[i], host[i].data(), host[i].size(), hipMemcpyHostToDevice));
+        rd[i].base = in.as<uint8_t>() + at[i];
+        rd[i].nbytes = (int64_t)host[i].size();
+        rd[i].nrec = rd[i].nbytes / gpu::kTeraRecordBytes;
+        rd[i].offsets = nullptr;
+      }
+      hipStream_t s = nullptr;
+      HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      try {
+        gpu::DeviceMerger merger(std::max<int64_t>(total, 1), std::max(K, 1));
+        merger.merge_fixed(rd, gf, merged.as<uint8_t>(), s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (out_bytes)
+          HIP_CHECK(hipMemcpy(PyBytes_AS_STRING(o), merged.as(), (size_t)out_bytes, hipMemcpyDeviceToHost));
+        passes = merger.last_passes();
+        overflow = merger.kway_overflow_cells();
+        bad = merger.bad_layout();
+        kway = merger.kway_enabled();
+      } catch (...) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+        throw;
+      }
+      (void)hipStreamDestroy(s);
+    }
+    py::dict d;
+    d["passes"] = passes;
+    d["overflow_cells"] = overflow;
+    d["bad_layout"] = bad;
+    d["kway"] = kway;
+    return py::make_tuple(out, d);
+  }, py::arg("runs"), py::arg("group_first") = py::none(), py::arg("device") = 0, py::arg("pad") = 0);
   m.def("codec_from_class", [](const std::string& c) {
     bool unsup = false;
     int v = (int)codec_from_class(c, &unsup);
