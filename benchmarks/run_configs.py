@@ -15,7 +15,8 @@
   spill               TeraSort whose map outputs live in pinned host DRAM (the spill tier used when a
                       job exceeds HBM): rounds are streamed H2D, merged on the GPU, delivered D2H.
   combine             wordcount over HBM-resident MOFs, 16 concurrent reduce tasks, 16 and 64 maps:
-                      mapred.uda.merge.combine none vs sum.int, and the F4 kernels phase by phase.
+                      mapred.uda.merge.combine none vs sum.int (--op: another op; sum.vint runs over
+                      VIntWritable counts), and the F4 kernels phase by phase.
                       --vocab N --tasks N --maps N: one low-duplication, few-task shape (several inner
                       rounds per task); --over-budget: the GPU hybrid, skipping against combining.
 
@@ -480,8 +481,32 @@ def _uniform_wordcount_runs(maps: int, tasks: int, rows: int, vocab: int, seed: 
     return out
 
 
+def _vint_count_runs(runs):
+    """The wordcount runs above (fixed-size records, IntWritable(1) values) with VIntWritable(1) values
+    instead: the same records and order, three bytes shorter each."""
+    import numpy as np
+    out = []
+    for parts in runs:
+        conv = []
+        for p in parts:
+            body = np.frombuffer(p, dtype=np.uint8)[:-2]
+            if len(body) == 0:
+                conv.append(bytes(p))
+                continue
+            size = 2 + int(body[0]) + 4  # one-byte key and value lengths, 4 value bytes
+            assert body[1] == 4 and len(body) % size == 0
+            rec = body.reshape(-1, size)
+            assert (rec[:, -4:] == (0, 0, 0, 1)).all()
+            v = np.ascontiguousarray(rec[:, :size - 3])
+            v[:, 1] = 1
+            v[:, -1] = 1
+            conv.append(v.tobytes() + b"\xff\xff")
+        out.append(conv)
+    return out
+
+
 def _combine_tasks(n, maps: int, tasks: int, rows: int, op: str, steps: int, warmup: int, vocab: int = 0,
-                   over_budget: str = "", lpq: bool = False) -> dict:
+                   over_budget: str = "", lpq: bool = False, value: str = "int") -> dict:
     """`tasks` concurrent reduce tasks over HBM-resident wordcount MOFs, `warmup` + `steps` times.
     over_budget ("skip" | "combine"): the MOFs in host memory instead and mapred.uda.gpu.merge.bytes at a
     quarter of a task's input, so every task takes the over-budget GPU hybrid (lpq: with LPQ spills in DRAM
@@ -490,6 +515,8 @@ def _combine_tasks(n, maps: int, tasks: int, rows: int, op: str, steps: int, war
     from uda_amd.utils.datagen import TEXT
     from uda_amd.utils.mof import encode_partitions
     runs = _uniform_wordcount_runs(maps, tasks, rows, vocab) if vocab else n.generate_runs("wordcount", maps, tasks, rows, 7)
+    if value == "vint":
+        runs = _vint_count_runs(runs)
     prov = UdaProvider()
     total = 0
     for m, parts in enumerate(runs):
@@ -561,27 +588,31 @@ def combine(args) -> dict:
     from uda_amd import native
     n = native()
     tasks = args.tasks or 16
-    out = {"config": f"wordcount, {tasks} reduce tasks over HBM-resident MOFs, combine none vs sum.int", "tasks": tasks}
+    cop = args.op
+    # the v ops run over the same records with VIntWritable counts (three bytes shorter each)
+    value = "vint" if cop in ("sum.vint", "sum.vlong") else "int"
+    out = {"config": f"wordcount ({value} counts), {tasks} reduce tasks over HBM-resident MOFs, combine none vs {cop}",
+           "tasks": tasks, "op": cop}
     if args.over_budget:
         # one shape, sum.int: the over-budget hybrid delivering the uncombined stream against combining
         rows = int(args.gb * 1e9 / args.maps / 17)
         out["config"] = f"wordcount, {tasks} reduce task(s) over host MOFs, device budget a quarter of the input"
         for mode in ("skip", "combine"):
-            out[f"over_budget_{mode}"] = _combine_tasks(n, args.maps, tasks, rows, "sum.int", steps=5, warmup=2,
-                                                        vocab=args.vocab, over_budget=mode, lpq=args.lpq)
+            out[f"over_budget_{mode}"] = _combine_tasks(n, args.maps, tasks, rows, cop, steps=5, warmup=2,
+                                                        vocab=args.vocab, over_budget=mode, lpq=args.lpq, value=value)
             print(f"# over budget, {mode}: {json.dumps(out[f'over_budget_{mode}'])}", file=sys.stderr, flush=True)
         return out
     shaped = bool(args.vocab or args.tasks)  # --vocab / --tasks: that one shape (--maps), task level only
     for maps in ((args.maps,) if shaped else (16, 64)):
         rows = int(args.gb * 1e9 / maps / 17)
-        for op in ("none", "sum.int"):
-            r = _combine_tasks(n, maps, tasks, rows, op, steps=5, warmup=2, vocab=args.vocab)
+        for op in ("none", cop):
+            r = _combine_tasks(n, maps, tasks, rows, op, steps=5, warmup=2, vocab=args.vocab, value=value)
             print(f"# maps={maps} {op}: {json.dumps(r)}", file=sys.stderr, flush=True)
             out[f"maps{maps}_{op}"] = r
-        a, b = out[f"maps{maps}_none"], out[f"maps{maps}_sum.int"]
+        a, b = out[f"maps{maps}_none"], out[f"maps{maps}_{cop}"]
         out[f"maps{maps}_records_per_group"] = round(b["combine_in_records"] / max(1, b["combine_groups"]), 1)
         out[f"maps{maps}_delivered_ratio"] = round(a["bytes_delivered"] / max(1, b["bytes_delivered"]), 1)
-        if shaped:
+        if shaped or cop != "sum.int":  # (the kernel phases are sum.int's)
             continue
         # kernel phases of one task's merge (last of three calls per op)
         env = dict(os.environ, UDA_GM_PROFILE="1")
@@ -618,6 +649,9 @@ def main() -> int:
     ap.add_argument("--vocab", type=int, default=0,
                     help="combine: words drawn uniformly from this many (default: the Zipf generator's 100 000)")
     ap.add_argument("--tasks", type=int, default=0, help="combine: concurrent reduce tasks (default 16)")
+    ap.add_argument("--op", default="sum.int",
+                    help="combine: the mapred.uda.merge.combine op measured against none (default sum.int); "
+                         "sum.vint / sum.vlong run over the same wordcount with VIntWritable counts")
     ap.add_argument("--lpq", action="store_true", help="combine --over-budget: mapred.uda.gpu.hybrid.direct=0 (LPQ spills)")
     ap.add_argument("--over-budget", action="store_true",
                     help="combine: host MOFs under a device budget of a quarter of a task's input, "

@@ -92,7 +92,7 @@ struct ReduceStats {
   int64_t host_fetched_bytes = 0;     // GPU device fetch: bytes of MOFs that were not device-resident
   int64_t local_read_bytes = 0;       // of those: read from the MOF files on this node (not over the network)
   std::string merge_path;             // which merge ran ("device-fixed10", "device-generic", ...)
-  // mapred.uda.merge.combine: "none", "sum.int", "sum.long", or "skipped-over-budget" when the GPU hybrid
+  // mapred.uda.merge.combine: "none", the op's name (uda/combine.h), or "skipped-over-budget" when the GPU hybrid
   // delivered the uncombined stream; merged records that went into the combiner and the groups (records)
   // it delivered. records / bytes_delivered / buffers count what was delivered.
   std::string combine = "none";

@@ -322,7 +322,8 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
   const bool gk_on = !(gk_env && *gk_env && std::atoi(gk_env) == 0);
   const bool gk = gk_on && K >= 2 && K <= kGkMaxRuns;
   // chunk = kv_buf - longest record keeps every delivery buffer within kv_buf
-  // (the longest record does not depend on the order: max over the side table's record lengths)
+  // (the longest record does not depend on the order: max over the side table's record lengths; a combine
+  // op that re-encodes the value can deliver a record up to combine_record_growth bytes longer than that)
   auto chunk_bytes = [&](const Elem*) {
     unsigned int* d_max = reinterpret_cast<unsigned int*>(scan_tmp_.as<int64_t>());
     launch_max_i32(ctx.reclen, total, d_max, s);
@@ -330,7 +331,7 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
     HIP_CHECK(hipMemcpyAsync(&m, d_max, 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     if ((int64_t)m > kv_buf) throw std::runtime_error("record larger than the delivery buffer");
-    return std::max<int64_t>(1, kv_buf - (int64_t)m);
+    return std::max<int64_t>(1, kv_buf - (int64_t)m - combine_record_growth(combine));
   };
   // F4 for merged elements [e0, e0 + n) whose records start at output byte b0: sizes -> scan ->
   // gather, then the delivery cuts of that range (relative) into host `raw` (pinned; complete once
@@ -367,7 +368,7 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
   if (combine != CombineOp::kNone && gk && on_round && want_rounds > 1) {
     reserve_combine(total);
     int* d_any = reinterpret_cast<int*>(cflag_.as<uint8_t>() + 8);
-    launch_combine_check_values(ctx, total, combine_value_bytes(combine), d_any, s);
+    launch_combine_check_values(ctx, total, combine, d_any, s);
     int any = 0;
     HIP_CHECK(hipMemcpyAsync(&any, d_any, 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
@@ -383,7 +384,6 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
     // round that delivers it. A group longer than a round delivers nothing until it closes.
     res.passes = 1;
     res.records = 0;
-    const int W = combine_value_bytes(combine);
     const int64_t chunk = chunk_bytes(cur);
     const int Q = (int)std::min<int64_t>(C, want_rounds);
     std::vector<int64_t> cb(Q + 1);
@@ -402,12 +402,17 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
     HIP_CHECK(hipMemcpyAsync(rb.data(), d_rb, 8 * (Q + 1), hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipMemsetAsync(gk_[0].flag.as(), 0, 4, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    // A round writes at most the records its cells added and the head of the group carried into it: its
-    // cuts are sized from rb with one delivery buffer of slack (the compacted size is read with the cuts).
+    // A round writes at most the records its cells added and the record of the group carried into it: the
+    // groups that began in the round consist of its records alone, and a combined group never has more bytes
+    // than its input records (uda/combine.h), so they stay within rb[q + 1] - rb[q]; the carried group's
+    // record is its head, of at most one delivery buffer, with the value re-encoded, which is at most
+    // combine_record_growth bytes longer (and need not be paid for by records of this round: the group can
+    // have closed with the round before). The cuts are sized from rb with that slack (the compacted size is
+    // read with the cuts).
     // Pinned host state per round, after the cuts: last head + 1, cell overflow, groups, bytes.
     std::vector<int64_t> coff(Q + 1, 0), nbuf(Q), cnt(Q, 0);
     for (int q = 0; q < Q; ++q) {
-      nbuf[q] = (rb[q + 1] - rb[q] + kv_buf + chunk - 1) / chunk;
+      nbuf[q] = (rb[q + 1] - rb[q] + kv_buf + combine_record_growth(combine) + chunk - 1) / chunk;
       coff[q + 1] = coff[q] + nbuf[q] + 1;
     }
     reserve_cuts(coff[Q] + 4 * (int64_t)Q);
@@ -444,9 +449,9 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
       cnt[q] = n;
       if (n == 0) return;  // one open group from a on: carried whole
       launch_exclusive_scan(d_heads + a, d_gidx + a, n, scan_tmp_.as<int64_t>(), s);
-      launch_combine_sums(ctx, nxt + a, d_gidx + a, n, W, d_sums + a, d_heads + a, s);
+      launch_combine_sums(ctx, nxt + a, d_gidx + a, n, combine, d_sums + a, d_heads + a, s);
       launch_exclusive_scan(d_heads + a, d_off + a, n, scan_tmp_.as<int64_t>(), s);
-      launch_gather_combine(ctx, nxt + a, n, d_gidx + a, d_off + a, d_sums + a, W, out + B, s);
+      launch_gather_combine(ctx, nxt + a, n, d_gidx + a, d_off + a, d_sums + a, combine, out + B, s);
       launch_buffer_cuts(d_off + a, n, chunk, nbuf[q], cuts_.as<int64_t>() + coff[q], s);
       HIP_CHECK(hipMemcpyAsync(cuts_host_.as<int64_t>() + coff[q], cuts_.as<int64_t>() + coff[q], 8 * (nbuf[q] + 1),
                                hipMemcpyDeviceToHost, s));
@@ -562,17 +567,16 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
     if (combine != CombineOp::kNone) {
       // ---- F4 under combine (combine.hip): heads -> group index -> sums and sizes -> offsets; the
       // compacted size is known only after the scans, so it is read here before the cuts are sized
-      const int W = combine_value_bytes(combine);
       reserve_combine(total);
       int64_t* d_gidx = gidx_.as<int64_t>();
       auto* d_sums = sums_.as<unsigned long long>();
       auto* d_bad = cflag_.as<unsigned long long>();
       phase("f4_chunk");
-      launch_combine_heads(ctx, cur, total, W, sizes_.as<int64_t>(), d_bad, s);
+      launch_combine_heads(ctx, cur, total, combine, sizes_.as<int64_t>(), d_bad, s);
       phase("f4c_heads");
       launch_exclusive_scan(sizes_.as<int64_t>(), d_gidx, total, scan_tmp_.as<int64_t>(), s);
       phase("f4c_group_scan");
-      launch_combine_sums(ctx, cur, d_gidx, total, W, d_sums, sizes_.as<int64_t>(), s);
+      launch_combine_sums(ctx, cur, d_gidx, total, combine, d_sums, sizes_.as<int64_t>(), s);
       phase("f4c_sums");
       launch_exclusive_scan(sizes_.as<int64_t>(), out_off_.as<int64_t>(), total, scan_tmp_.as<int64_t>(), s);
       phase("f4_scan");
@@ -583,7 +587,7 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
       HIP_CHECK(hipMemcpyAsync(&cbytes, out_off_.as<int64_t>() + total, 8, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
       if (bad != ~0ull) {
-        // the first record (in merged order) the op cannot sum: its key and value length for the error
+        // the first record (in merged order) the op cannot fold: its key and value length for the error
         Elem e;
         HIP_CHECK(hipMemcpy(&e, cur + bad, sizeof(Elem), hipMemcpyDeviceToHost));
         const uint64_t g = e.lo & 0xFFFFFFFFFFFFull;
@@ -602,7 +606,7 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
       res.bytes = cbytes;
       const int64_t nbuf = (cbytes + chunk - 1) / chunk;
       reserve_cuts(nbuf + 1);
-      launch_gather_combine(ctx, cur, total, d_gidx, out_off_.as<int64_t>(), d_sums, W, out, s);
+      launch_gather_combine(ctx, cur, total, d_gidx, out_off_.as<int64_t>(), d_sums, combine, out, s);
       phase("f4c_gather_combine");
       launch_buffer_cuts(out_off_.as<int64_t>(), total, chunk, nbuf, cuts_.as<int64_t>(), s);
       HIP_CHECK(hipMemcpyAsync(cuts_host_.as<int64_t>(), cuts_.as<int64_t>(), 8 * (nbuf + 1), hipMemcpyDeviceToHost, s));

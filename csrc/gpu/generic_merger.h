@@ -41,13 +41,15 @@ class GenericMerger {
   // on this thread while the device already merges the next round (so a caller's D2H of the round
   // overlaps the merge). Without the single-pass path it is called once for the whole output.
   //
-  // combine (uda/combine.h): equal keys are summed into their group's first record before the gather
-  // (combine.hip); the output then holds one record per distinct key of the runs. An input of at most
+  // combine (uda/combine.h): equal keys are folded (summed, or their minimum / maximum taken) into their
+  // group's first record before the gather (combine.hip); the output then holds one record per distinct key
+  // of the runs and is never larger than the input, although under the ops that re-encode the value a
+  // record can be up to 8 bytes longer than its group's first, which the delivery chunk allows for. An input of at most
   // round_bytes is combined whole and on_round is called once (the output's size is known only after the
   // group scan). A larger one is streamed in key-range rounds that end on group boundaries: a round hands
   // over the groups that are closed and carries its open last group into the next round, a round that
   // closes no group makes no call, and the final call has last = true. A record whose value the op
-  // cannot sum throws UdaError and nothing is written. kNone: the merge as it is without a combiner.
+  // cannot read throws UdaError and nothing is written. kNone: the merge as it is without a combiner.
   using RoundFn = std::function<void(const std::vector<int64_t>& cuts, int64_t records, bool last)>;
   GenericMergeResult merge(const std::vector<const uint8_t*>& runs, const std::vector<int64_t>& run_bytes,
                            int kind, uint8_t* out, int64_t out_cap, int64_t kv_buf, hipStream_t s,

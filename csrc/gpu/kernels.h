@@ -17,6 +17,7 @@
 #include <cstdint>
 
 namespace uda {
+enum class CombineOp : int;  // uda/combine.h
 namespace gpu {
 
 // 16-byte merge element. Ordering is lexicographic on (hi, lo).
@@ -220,31 +221,35 @@ void launch_buffer_cuts(const int64_t* out_off, int64_t n, int64_t chunk, int64_
                         hipStream_t s);
 
 // ---------------------------------------------------------------- reduce-side combiner (combine.hip)
-// Equal keys of the merged order summed into their group's first record (uda/combine.h); W = 4
-// (sum.int) or 8 (sum.long) value bytes.
+// Equal keys of the merged order folded into their group's first record (uda/combine.h): sums, min / max
+// over W = 4 or 8 value bytes, and sums of one VInt / VLong (the v ops, whose records change length).
 constexpr int kCombineTile = 256;  // merged elements per workgroup of launch_combine_sums
 // heads[i] = 1 if merged element i starts a group (i == 0 or its key differs from i - 1's), else 0.
-// *bad = lowest i whose record's value is not W bytes long, ~0 if none (set here).
-void launch_combine_heads(GenericKeyCtx ctx, const Elem* order, int64_t n, int W, int64_t* heads,
+// *bad = lowest i whose record's value the op cannot read (combine_value_ok), ~0 if none (set here).
+void launch_combine_heads(GenericKeyCtx ctx, const Elem* order, int64_t n, CombineOp op, int64_t* heads,
                           unsigned long long* bad, hipStream_t s);
-// Streamed rounds. *any_bad = 1 if any of the n records of the side tables has a value that is not W bytes
-// long, else 0 (set here); independent of the merged order, so it runs before F3.
-void launch_combine_check_values(GenericKeyCtx ctx, int64_t n, int W, int* any_bad, hipStream_t s);
+// Streamed rounds. *any_bad = 1 if any of the n records of the side tables has a value the op cannot read,
+// else 0 (set here); independent of the merged order, so it runs before F3.
+void launch_combine_check_values(GenericKeyCtx ctx, int64_t n, CombineOp op, int* any_bad, hipStream_t s);
 // heads[i] for the merged elements i in [i0, i1) (i0 > 0 compares with element i0 - 1), and the round
 // close: *last_head = max(*last_head, 1 + the highest head position in [i0, i1)); the caller zeroes it.
 void launch_combine_round_heads(GenericKeyCtx ctx, const Elem* order, int64_t i0, int64_t i1, int64_t* heads,
                                 unsigned long long* last_head, hipStream_t s);
-// gidx = exclusive scan of heads (n + 1 entries). sums[q] = sum of the values of group q modulo 2^64
-// (n entries of room, zeroed here; values of records flagged in *bad count as 0), and the F4 sizes
-// under combine: sizes[i] = record size of a head, 0 for any other element.
-void launch_combine_sums(GenericKeyCtx ctx, const Elem* order, const int64_t* gidx, int64_t n, int W,
+// gidx = exclusive scan of heads (n + 1 entries). sums[q] = fold of the values of group q (n entries of
+// room, zeroed here; values of records flagged in *bad count as the identity): the sum modulo 2^64, or for
+// min / max an order-preserving image of the extreme that launch_gather_combine maps back. And the F4 sizes
+// under combine: sizes[i] = size of the delivered record of a head, 0 for any other element. Under the v ops
+// that size depends on the finished sum, so a second small kernel writes it after the fold.
+void launch_combine_sums(GenericKeyCtx ctx, const Elem* order, const int64_t* gidx, int64_t n, CombineOp op,
                          unsigned long long* sums, int64_t* sizes, hipStream_t s);
 // F4 under combine: the head records copied to out + out_off[i] (out_off = exclusive scan of those
-// sizes), their last W bytes replaced by the big-endian low 8W bits of their group's sum.
+// sizes). Fixed-width ops: their last W bytes replaced by the big-endian low 8W bits of the group's folded
+// value. v ops: their value replaced by the canonical VInt of the sum and the one-byte value-length header
+// set to its length; nothing is read past the head's headers and key.
 // launch_buffer_cuts runs on these offsets unchanged: an element of size 0 has the offset of the next
 // head (or the total), so the first offset >= j * chunk it finds is still a record boundary.
 void launch_gather_combine(GenericKeyCtx ctx, const Elem* elems, int64_t n, const int64_t* gidx,
-                           const int64_t* out_off, const unsigned long long* sums, int W, uint8_t* out,
+                           const int64_t* out_off, const unsigned long long* sums, CombineOp op, uint8_t* out,
                            hipStream_t s);
 
 // ---------------------------------------------------------------- gather / serialize (F4)

@@ -1520,7 +1520,8 @@ PYBIND11_MODULE(_uda_native, m) {
   });
   // Merge IFile runs (any bytes-like objects, read in place) on the device. Returns
   // (merged bytes, buffer cuts, records, merge passes, device merge ms, runs indexed serially, records merged).
-  // combine: "none", "sum.int" or "sum.long" (uda/combine.h): records then counts the groups delivered.
+  // combine: "none" or an op of uda/combine.h (sum.int, sum.long, min.int, max.int, min.long, max.long,
+  // sum.vint, sum.vlong): records then counts the groups delivered.
   m.def("gpu_merge_runs", [](const py::list& runs, const std::string& key_class, int64_t kv_buf, int device,
                              const std::string& combine) {
     KeyKind kind = key_kind_from_class(key_class.c_str());

@@ -16,8 +16,12 @@ last_stats: dict = {}  # timing of the most recent merge_runs call (device merge
 
 def merge_runs(runs: list[bytes], key_class: str, device: str = "gpu", kv_buf: int = 1 << 20,
                gpu_index: int = 0, combine: str = "none"):
-    """combine: "none", "sum.int" or "sum.long" (mapred.uda.merge.combine): equal keys are summed into the
-    first record of their group, on the device (csrc/gpu/combine.hip) or by the host reference."""
+    """combine: "none" or an op of mapred.uda.merge.combine: equal keys are folded into the first record of
+    their group, on the device (csrc/gpu/combine.hip) or by the host reference.
+      sum.int, sum.long                      4 / 8-byte big-endian values, wrapping sum
+      min.int, max.int, min.long, max.long   the same values, signed minimum / maximum
+      sum.vint, sum.vlong                    one Hadoop VInt / VLong per value; the sum is re-encoded
+                                             canonically, so a delivered record can change length"""
     n = native()
     if device == "gpu":
         if n.device_count() <= 0:

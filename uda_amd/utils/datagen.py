@@ -12,7 +12,7 @@ from __future__ import annotations
 import random
 
 from .._native import native
-from .ifile import encode_stream, text
+from .ifile import encode_stream, text, vint_encode
 
 TEXT = "org.apache.hadoop.io.Text"
 INT = "org.apache.hadoop.io.IntWritable"
@@ -58,7 +58,12 @@ def terasort(num_maps: int, reducers: int, rows_per_map: int, seed: int = 1):
     return _finish(maps, TEXT)
 
 
-def wordcount(num_maps: int, reducers: int, words_per_map: int, vocab: int = 5000, seed: int = 2):
+def wordcount(num_maps: int, reducers: int, words_per_map: int, vocab: int = 5000, seed: int = 2, value: str = "int"):
+    """value: how a count is written. "int": IntWritable, 4 bytes big-endian; "vint" / "vlong": VIntWritable /
+    VLongWritable, one Hadoop VInt (a count below 128 is one byte). The draws do not depend on it."""
+    if value not in ("int", "vint", "vlong"):
+        raise ValueError("wordcount: value must be int, vint or vlong")
+    enc = (lambda c: c.to_bytes(4, "big")) if value == "int" else vint_encode
     rng = random.Random(seed)
     words = [("w%06d" % i).encode() for i in range(vocab)]
     weights = [1.0 / (i + 1) for i in range(vocab)]  # Zipf-like skew
@@ -69,7 +74,7 @@ def wordcount(num_maps: int, reducers: int, words_per_map: int, vocab: int = 500
             counts[w] = counts.get(w, 0) + 1  # map-side combiner
         parts = [[] for _ in range(reducers)]
         for w, c in counts.items():
-            parts[partition_of(w, reducers)].append((text(w), c.to_bytes(4, "big")))
+            parts[partition_of(w, reducers)].append((text(w), enc(c)))
         maps.append(parts)
     return _finish(maps, TEXT)
 
