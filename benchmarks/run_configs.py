@@ -633,10 +633,74 @@ def combine(args) -> dict:
     return out
 
 
+def checksum(args) -> dict:
+    """IFile checksum trailers (mapred.uda.ifile.checksum). First the CRC32 kernels alone: 16 ranges of equal
+    size filling --gb, next to launch_batched_copy of the same bytes in the same process (hipEvents around
+    each launch, 3 warm-ups, 10 repetitions). Then 16 concurrent reduce tasks over HBM-resident
+    TeraSort-shaped MOFs that carry trailers, `auto` (verified on the device) against `off` (stripped only):
+    2 warm-up steps of each, then 5 steps of each, alternating."""
+    from uda_amd import native
+    from uda_amd.bridge import UdaConsumer, UdaProvider
+    from uda_amd.utils.datagen import TEXT
+    from uda_amd.utils.mof import encode_partitions
+    n = native()
+    tasks = args.tasks or 16
+    out = {"config": f"IFile checksum: CRC32 kernel vs batched copy; {tasks} TeraSort tasks over HBM MOFs, auto vs off"}
+    part = int(args.gb * 1e9 / 16) & ~255
+    k = n.gpu_crc32_bench(16, part, 3, 10)
+    gbps = lambda ms: k["bytes"] / (ms * 1e-3) / 1e9  # noqa: E731
+    crc, cpy = sorted(gbps(ms) for ms in k["crc_ms"]), sorted(gbps(ms) for ms in k["copy_ms"])
+    out["kernel"] = {"bytes": k["bytes"], "ranges": 16, "repeatable": k["repeatable"],
+                     "crc32_gbps_min_med_max": [round(crc[0], 1), round(crc[len(crc) // 2], 1), round(crc[-1], 1)],
+                     "batched_copy_gbps_min_med_max": [round(cpy[0], 1), round(cpy[len(cpy) // 2], 1), round(cpy[-1], 1)],
+                     "crc32_over_copy": round(crc[len(crc) // 2] / cpy[len(cpy) // 2], 2)}
+    print(f"# kernel: {json.dumps(out['kernel'])}", file=sys.stderr, flush=True)
+    rows = int(args.gb * 1e9 / args.maps / 104)  # per map, spread over the tasks' partitions
+    runs = n.generate_runs("terasort", args.maps, tasks, rows, 7)
+    prov = UdaProvider()
+    total = 0
+    for m, parts in enumerate(runs):
+        data, index = encode_partitions(parts, checksum=True)
+        total += len(data) - 6 * len(parts)
+        prov.add_mof_device("job_ck", f"attempt_ck_m_{m:06d}_0", data, index)
+    del runs
+    base = {"mapred.uda.merge.backend": "gpu", "mapred.uda.gpu.fetch": "device"}
+    res = {"auto": [], "off": []}
+    last = {}
+    for step in range(2 + 5):
+        for mode in ("auto", "off"):
+            conf = dict(base, **{"mapred.uda.ifile.checksum": mode})
+            cons = [UdaConsumer(args.maps, "job_ck", f"attempt_ck_r_{r:06d}_{step}{mode}", TEXT, conf=conf, keep_records=False)
+                    for r in range(tasks)]
+            t0 = time.perf_counter()
+            for m in range(args.maps):
+                for r, c in enumerate(cons):
+                    c.fetch("localhost", "job_ck", f"attempt_ck_m_{m:06d}_0", r)
+            for c in cons:
+                c.wait(3600)
+            wall = time.perf_counter() - t0
+            last[mode] = [c.close() for c in cons]
+            if step >= 2:
+                res[mode].append(total / wall / 1e9)
+    prov.close()
+    out["input_gb"] = round(total / 1e9, 3)
+    for mode in ("auto", "off"):
+        st = last[mode]
+        out[mode] = {"input_gbps": [round(x, 2) for x in sorted(res[mode])],
+                     "input_gbps_min_max": [round(min(res[mode]), 2), round(max(res[mode]), 2)],
+                     "ifile_checksum": sorted({s["ifile_checksum"] for s in st}),
+                     "merge_path": sorted({s["merge_path"] for s in st}),
+                     "checksum_partitions": sum(s["checksum_partitions"] for s in st),
+                     "checksum_bytes": sum(s["checksum_bytes"] for s in st),
+                     "task_gpu_checksum_ms_mean": round(sum(s["gpu_checksum_ms"] for s in st) / len(st), 3),
+                     "task_merge_ms_mean": round(sum(s["merge_ms"] for s in st) / len(st), 2)}
+    return out
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("config", choices=["wordcount_loopback", "wordcount_tcp", "cpu_reference", "secondary_sort", "spill", "decode", "aio",
-                                       "netmerger", "radix", "hybrid_budget", "combine", "combine_kernels"])
+                                       "netmerger", "radix", "hybrid_budget", "combine", "combine_kernels", "checksum"])
     ap.add_argument("--dir", default="/tmp")
     ap.add_argument("--codec", default="snappy", choices=["snappy", "lzo", "lz4"])
     ap.add_argument("--gb", type=float, default=1.0)

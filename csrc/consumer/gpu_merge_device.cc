@@ -343,6 +343,8 @@ bool ReduceTask::merge_gpu_device(bool probe) {
   struct Part {
     const uint8_t* dptr = nullptr;
     int64_t part_len = 0;
+    int64_t raw_len = 0;  // the index's rawLength, as the provider answered it (<= 0: it did not say)
+    std::string map_id;
   };
   std::vector<std::unique_ptr<Part>> parts;
   int64_t host_bytes = 0, descriptors = 0, unmapped = 0;
@@ -413,6 +415,8 @@ bool ReduceTask::merge_gpu_device(bool probe) {
     for (size_t i = 0; i < batch.size(); ++i) {
       const FetchAck& a = acks[i];
       auto part = std::make_unique<Part>();
+      part->raw_len = a.raw_len;
+      part->map_id = batch[i].map_id;
       std::string why;
       const uint8_t* dp = nullptr;
       const auto tm = std::chrono::steady_clock::now();
@@ -506,6 +510,37 @@ bool ReduceTask::merge_gpu_device(bool probe) {
     st_.host_fetched_bytes = host_bytes;
     st_.local_read_bytes = local_bytes;
   }
+  // IFile checksum trailers (uda/ifile.h). Every partition has its device address now: the trailers are
+  // stripped here, where the parts' lengths are set, so everything below sees what it sees without them,
+  // and (mapred.uda.ifile.checksum=auto) one batched CRC launch over the partitions as fetched goes on the
+  // task's stream ahead of the decode and the merge. Its result is read at the first synchronize of that
+  // stream the task makes anyway; no record is delivered before. A job without trailers launches nothing.
+  const bool verify = checksum_ == ChecksumMode::kAuto;
+  int64_t trailers = 0;
+  auto launch_checksums = [&](const std::vector<int>& tails) {
+    std::vector<gpu::DeviceChecksum::Item> items;
+    for (size_t i = 0; i < parts.size(); ++i) {
+      if (!tails[i]) continue;
+      ++trailers;
+      parts[i]->part_len -= tails[i];
+      if (verify) items.push_back(gpu::DeviceChecksum::Item{parts[i]->dptr, parts[i]->part_len, parts[i]->map_id, false, 0});
+    }
+    if (!items.empty()) ws.checksum.launch(std::move(items), s);
+  };
+  // synced: s has been synchronized since the launch
+  auto finish_checksums = [&](bool synced) {
+    if (ws.checksum.pending()) {
+      ws.checksum.finish(s, synced);
+      note_checksum(ws.checksum.partitions(), ws.checksum.bytes(), ws.checksum.ms());
+    } else if (trailers > 0 && !verify) {
+      note_checksum(0, 0);
+    }
+  };
+  if (codec_ == Codec::kNone) {
+    std::vector<int> tails;
+    for (const auto& p : parts) tails.push_back(ifile_trailer_bytes(p->raw_len, p->part_len));
+    launch_checksums(tails);
+  }
   // HBM admission (gpu/hbm_ledger.h): the task's device working set -- decoded partitions, the
   // key-range round's output slots and merge tables -- is reserved before it is allocated, under the
   // device's byte budget shared with the provider's store and every other task on the node. A round
@@ -535,7 +570,19 @@ bool ReduceTask::merge_gpu_device(bool probe) {
     gpu::BlockPlan bp;
     std::vector<int64_t> roff;
     int64_t blocks = 0;
-    const bool dev_frames = gpu::plan_block_streams_device(codec_, cp, cl, &bp, ws.frame_scratch, ws.frame_descs, s);
+    // (the framing walk finds the trailers; the checksum kernels go between its two passes, and the second
+    // pass's synchronize brings their result)
+    std::vector<int> tails;
+    const bool dev_frames = gpu::plan_block_streams_device(codec_, cp, cl, &bp, ws.frame_scratch, ws.frame_descs, s,
+                                                           &tails, launch_checksums);
+    if (dev_frames) {
+      finish_checksums(!bp.descs.empty());
+      for (size_t i = 0; i < parts.size(); ++i)
+        if (tails[i] && parts[i]->raw_len > 0 && bp.raw_offset[i + 1] - bp.raw_offset[i] != parts[i]->raw_len)
+          throw UdaError("compressed map output " + parts[i]->map_id + " decodes to " +
+                         std::to_string(bp.raw_offset[i + 1] - bp.raw_offset[i]) + " bytes, its index says " +
+                         std::to_string(parts[i]->raw_len));
+    }
     // TeraSort-shaped partitions: decode per key-range round, only the blocks each round covers, so the
     // task's device memory is round-sized instead of its decoded partitions (DecompressorWrapper decodes
     // block by block next to the merge too, src/Merger/DecompressorWrapper.cc:85-114)
@@ -618,11 +665,20 @@ bool ReduceTask::merge_gpu_device(bool probe) {
       for (size_t i = 0; i < cp.size(); ++i) {
         std::vector<uint8_t> c((size_t)cl[i]);
         if (cl[i] > 0) HIP_CHECK(hipMemcpy(c.data(), cp[i], (size_t)cl[i], hipMemcpyDefault));
-        BlockDecoder dec(codec_);
-        dec.feed(c.data(), c.size());
-        std::vector<uint8_t> raw, buf(1 << 20);
-        for (size_t n; (n = dec.read(buf.data(), buf.size())) > 0;) raw.insert(raw.end(), buf.begin(), buf.begin() + (long)n);
-        if (!dec.idle()) throw UdaError("truncated compressed partition");
+        int tail = 0;  // (the bytes are decoded here, on the host: so is their checksum)
+        std::vector<uint8_t> raw = host_decode_partition(codec_, c.data(), (int64_t)c.size(), &tail);
+        if (tail) {
+          ++trailers;
+          const int64_t body = (int64_t)c.size() - tail;
+          if (parts[i]->raw_len > 0 && (int64_t)raw.size() != parts[i]->raw_len)
+            throw UdaError("compressed map output " + parts[i]->map_id + " decodes to " + std::to_string(raw.size()) +
+                           " bytes, its index says " + std::to_string(parts[i]->raw_len));
+          if (verify) {
+            const uint32_t stored = ifile_stored_checksum(c.data() + body), got = crc32_ieee(c.data(), (size_t)body);
+            if (stored != got) throw UdaError(ifile_checksum_mismatch(parts[i]->map_id, stored, got, body));
+            note_checksum(1, body);
+          }
+        }
         roff.push_back(roff.back() + (int64_t)raw.size());
         raws.push_back(std::move(raw));
       }
@@ -653,7 +709,9 @@ bool ReduceTask::merge_gpu_device(bool probe) {
     d.offsets = nullptr;
     runs.push_back(d);
   }
-  if (fixed && gpu::runs_are_fixed10(runs, s)) {
+  const bool fixed10 = fixed && gpu::runs_are_fixed10(runs, s);  // (synchronizes s)
+  finish_checksums(fixed && !runs.empty());
+  if (fixed10) {
     gpu::DeviceReduceConfig cfg;
     cfg.device = device;
     cfg.kv_buf_bytes = kv_buf_size_;

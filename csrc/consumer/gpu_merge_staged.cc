@@ -46,6 +46,7 @@
 #include "rpq_plan.h"
 #include "uda/aio.h"
 #include "uda/fault.h"
+#include "uda/ifile.h"
 #include "uda/log.h"
 #include "uda/safe_file.h"
 #include "uda/trace.h"
@@ -95,7 +96,9 @@ struct DirectPlan {
 // ReduceTask::merge_gpu() as an object: what were the function's locals are members, its steps methods.
 class StagedMerge {
  public:
-  explicit StagedMerge(ReduceTask& t) : t_(t), maps_(t.init_.num_maps), device_(t.device_) {}
+  explicit StagedMerge(ReduceTask& t) : t_(t), maps_(t.init_.num_maps), device_(t.device_) {
+    map_ids_.reserve((size_t)std::max(maps_, 0));  // (read by the LPQ thread while the fetch appends: never regrown)
+  }
   void run();
 
  private:
@@ -117,6 +120,8 @@ class StagedMerge {
   void merge_spill(std::vector<Span> jg, std::vector<std::string> ids, EarlyStager* st);
   void index_spans(const std::vector<Span>& spans, size_t first, std::vector<SpillRun>* out) const;
   void count_decoded(int64_t n);
+  void count_checksums(const DeviceMergeOut& m);
+  int span_id(const std::string& map_id);
   // delivery
   void deliver(const DeviceMergeOut& m, bool last, hipStream_t ds, DeviceWorkspace& w);
   gpu::GenericMerger::RoundFn round_sink(bool last_phase);
@@ -159,6 +164,12 @@ class StagedMerge {
   double fetch_ms_ = 0, prog_fetch_ms_ = -1;
   std::atomic<int64_t> combine_in_{0};  // (the LPQ thread counts its merges' input too)
   bool combine_skipped_ = false;
+  // IFile checksum trailers (uda/ifile.h, mapred.uda.ifile.checksum): partitions whose trailer was stripped,
+  // and of those verified on the device. The online and progressive merges verify every one; over budget
+  // (LPQ spills, RPQ rounds over partitions that never lie whole in HBM) they are stripped unverified.
+  std::atomic<int64_t> trailers_{0}, verified_{0};
+  std::vector<std::string> map_ids_;  // Span::id -> map output, for the mismatch message
+  ChecksumPolicy verify_ck_, strip_ck_;
   // over budget under mapred.uda.merge.combine.over.budget=combine: the op of the RPQ rounds, and of the
   // LPQ merges (kNone under an LPQ checkpoint: its spills stay as a resumed attempt expects them)
   CombineOp hybrid_combine_ = CombineOp::kNone, lpq_combine_ = CombineOp::kNone;
@@ -338,6 +349,8 @@ void StagedMerge::read_conf() {
   // LPQ checkpoint (disk tier): spills_[0, checkpointed_) are fsynced, indexed in <path>.idx and
   // listed in the manifest; a failed attempt keeps them for the next one
   ckpt_ = t_.checkpoint_ && tier_ == "disk";
+  verify_ck_ = ChecksumPolicy{t_.checksum_ == ChecksumMode::kAuto, &map_ids_};
+  strip_ck_ = ChecksumPolicy{false, &map_ids_};
   hybrid_combine_ = t_.combine_over_budget_ ? t_.combine_ : CombineOp::kNone;
   lpq_combine_ = ckpt_ ? CombineOp::kNone : hybrid_combine_;
   // Progressive phases (ProgFetch). Default (-1): 4 phases when the task is the only staged GPU merge on
@@ -496,7 +509,13 @@ void StagedMerge::start_direct_prog(const std::vector<std::shared_ptr<MofFetcher
   // 256 KiB for GB partitions, finer for small tasks under a small budget
   dp.spacing = std::clamp<int64_t>(budget_ / 2 / (4 * std::max(1, dp.K)), 4 << 10, kSampleSpacing);
   dp.f = ready;
-  for (auto& f : ready) dp.cap.push_back(std::max<int64_t>(f->part_len(), 0));
+  for (auto& f : ready) {
+    const int64_t cap = std::max<int64_t>(f->part_len(), 0);
+    const int tail = ifile_trailer_bytes(f->raw_len(), cap);  // (uncompressed partitions only get here)
+    dp.cap.push_back(cap);
+    dp.body.push_back(cap - tail);
+    if (tail) ++trailers_;
+  }
   const size_t K = (size_t)dp.K;
   // each partition's pinned span is taken by the thread that fetches its first phase (in parallel,
   // beside the first fetches: pinning GBs serially here held up the whole fetch)
@@ -533,7 +552,11 @@ void StagedMerge::start_prog_fetch(const std::vector<std::shared_ptr<MofFetcher>
   pf.f = ready;
   for (auto& f : ready) {
     const int64_t cap = std::max<int64_t>(f->part_len(), 0);
+    const int tail = ifile_trailer_bytes(f->raw_len(), cap);  // (uncompressed: the stager needs them so)
     pf.cap.push_back(cap);
+    pf.body.push_back(cap - tail);
+    pf.id.push_back(span_id(f->params().map_id));
+    if (tail) ++trailers_;
     pf.dst.push_back(fill_mem_->alloc((size_t)std::max<int64_t>(cap, 1)));
     pf.dev.push_back(stager_->reserve(cap));
   }
@@ -599,8 +622,12 @@ void StagedMerge::drain_batch(const std::vector<std::shared_ptr<MofFetcher>>& re
           off = t_.fetch_direct(f.params(), dst[k], off, cap, depth_, on_prefix, stage_step);
         }
         if (dev && stage_step <= 0) stager->copy(dst[k], dev, off);
-        got[k] = Span{dst[k], off, dev};
-        if (index_now) sub_idx[k] = index_partition(dst[k], off);
+        // an uncompressed partition's IFile checksum trailer stays behind its span (in pinned memory and in
+        // the staged copy); a compressed one's is found by the framing walk of the merge that decodes it
+        const int tail = stage_codec_ == Codec::kNone ? ifile_trailer_bytes(f.raw_len(), off) : 0;
+        if (tail) ++trailers_;
+        got[k] = Span{dst[k], off - tail, dev, tail, f.raw_len()};
+        if (index_now) sub_idx[k] = index_partition(dst[k], off - tail);
       } else {  // host decode: decoded length unknown up front
         std::vector<uint8_t> buf((size_t)t_.buffer_size_);
         for (int64_t n; (n = f.pull(buf.data(), (int64_t)buf.size())) > 0;)
@@ -626,6 +653,7 @@ void StagedMerge::drain_batch(const std::vector<std::shared_ptr<MofFetcher>>& re
       std::memcpy(p, host_decoded[k].data(), host_decoded[k].size());
       got[k] = Span{p, (int64_t)host_decoded[k].size()};
     }
+    got[k].id = span_id(ready[sub[k]]->params().map_id);
     group_.push_back(got[k]);
     if (index_now) direct_runs_.push_back(std::move(sub_idx[k]));
     if (ckpt_) group_ids_.push_back(ready[sub[k]]->params().map_id);
@@ -719,6 +747,21 @@ void StagedMerge::count_decoded(int64_t n) {
   t_.st_.device_decoded_blocks += n;
 }
 
+// trailers a device merge stripped from its runs (compressed runs: found by its framing walk; uncompressed
+// ones were counted when their spans were made) and those it verified
+void StagedMerge::count_checksums(const DeviceMergeOut& m) {
+  if (stage_codec_ != Codec::kNone) trailers_ += m.trailers;
+  if (m.checksum_parts > 0) {
+    verified_ += m.checksum_parts;
+    t_.note_checksum(m.checksum_parts, m.checksum_bytes, m.checksum_ms);
+  }
+}
+
+int StagedMerge::span_id(const std::string& map_id) {
+  map_ids_.push_back(map_id);
+  return (int)map_ids_.size() - 1;
+}
+
 // LPQ: merge one group on the device and spill it with its sparse index. Runs on the LPQ thread,
 // one group at a time, while the fetch fills the next group (the reference's fetcher running ahead
 // of the LPQ merges, MergeManager.cc:202-288).
@@ -732,13 +775,16 @@ void StagedMerge::merge_spill(std::vector<Span> jg, std::vector<std::string> ids
   // wrapping sums are associative, so the delivered bits do not depend on the grouping)
   DeviceMergeOut m;
   try {
-    m = device_merge(ws, jg, stage_codec_, t_.kind_, lpq_spacing(), s, nullptr, false, lpq_combine_);
+    m = device_merge(ws, jg, stage_codec_, t_.kind_, lpq_spacing(), s, nullptr, false, lpq_combine_, 256ll << 20,
+                     &strip_ck_);
   } catch (const std::runtime_error& e) {
     // the merge's cuts are the index samples, and a cut spacing bounds the record size: a record longer than
     // the finer spacing of a combined spill takes the usual one
     if (lpq_spacing() == kSampleSpacing || !std::strstr(e.what(), "record larger than the delivery buffer")) throw;
-    m = device_merge(ws, jg, stage_codec_, t_.kind_, kSampleSpacing, s, nullptr, false, lpq_combine_);
+    m = device_merge(ws, jg, stage_codec_, t_.kind_, kSampleSpacing, s, nullptr, false, lpq_combine_, 256ll << 20,
+                     &strip_ck_);
   }
+  count_checksums(m);
   if (lpq_combine_ != CombineOp::kNone) combine_in_ += m.records_in;
   if (tl) {
     trace::host_event("lpq_flush", (int64_t)jg.size(), 0, tl, tm);
@@ -1030,7 +1076,7 @@ void StagedMerge::run_progressive() {
       std::vector<char> fin((size_t)K);
       for (int k = 0; k < K; ++k) {
         win[(size_t)k] = pf.dev[(size_t)k] + start[(size_t)k];
-        avail[(size_t)k] = land[(size_t)k] - start[(size_t)k];
+        avail[(size_t)k] = std::min(land[(size_t)k], pf.body[(size_t)k]) - start[(size_t)k];  // (never the trailer)
         fin[(size_t)k] = land[(size_t)k] >= pf.cap[(size_t)k];
       }
       const auto tp = std::chrono::steady_clock::now();
@@ -1051,8 +1097,23 @@ void StagedMerge::run_progressive() {
     } else {
       prog_fetch_ms_ = std::chrono::duration<double, std::milli>(pf.t_end - t0_).count();
       for (int k = 0; k < K; ++k)
-        spans[(size_t)k] = Span{pf.dst[(size_t)k] + start[(size_t)k], pf.cap[(size_t)k] - start[(size_t)k],
+        spans[(size_t)k] = Span{pf.dst[(size_t)k] + start[(size_t)k], pf.body[(size_t)k] - start[(size_t)k],
                                 pf.dev[(size_t)k] + start[(size_t)k]};
+      // every partition lies whole in HBM now: their IFile checksums, before the last key range is merged
+      // (earlier ranges are delivered already, as with any failure this late)
+      std::vector<gpu::DeviceChecksum::Item> items;
+      for (int k = 0; k < K && verify_ck_.verify; ++k)
+        if (pf.body[(size_t)k] < pf.cap[(size_t)k])
+          items.push_back(gpu::DeviceChecksum::Item{pf.dev[(size_t)k], pf.body[(size_t)k], map_ids_[(size_t)pf.id[(size_t)k]],
+                                                    false, 0});
+      if (!items.empty()) {
+        ws.checksum.reset();
+        ws.checksum.launch(std::move(items), s_);
+        ws.checksum.finish(s_, false);
+        verified_ += ws.checksum.partitions();
+        t_.note_checksum(ws.checksum.partitions(), ws.checksum.bytes(), ws.checksum.ms());
+        ws.checksum.reset();
+      }
     }
     const DeviceMergeOut pm =
         device_merge(ws, spans, Codec::kNone, t_.kind_, kv_, s_, round_sink(last_phase), false, t_.combine_,
@@ -1071,7 +1132,8 @@ void StagedMerge::run_online() {
     ws_->h2d_ms += ms_since(tf);
   }
   DeviceMergeOut m = device_merge(*ws_, group_, stage_codec_, t_.kind_, kv_, s_, round_sink(true), false, t_.combine_,
-                                  t_.merge_round_bytes_);
+                                  t_.merge_round_bytes_, &verify_ck_);
+  count_checksums(m);
   combine_in_ += m.records_in;
   count_decoded(m.decoded_blocks);
 }
@@ -1228,7 +1290,10 @@ void StagedMerge::finish() {
   ws3_lease_.clean = true;
   stager_lease_.clean = true;
   stager_lease2_.clean = true;
+  if (trailers_ > 0 && !verify_ck_.verify) t_.note_checksum(0, 0);  // stripped, mapred.uda.ifile.checksum=off
   std::lock_guard<std::mutex> g(t_.st_mu_);
+  if (trailers_ > verified_ && verify_ck_.verify && st_.ifile_checksum != "verified")
+    st_.ifile_checksum = "skipped-over-budget";  // (host-decoded partitions are verified as they are pulled)
   if (combine_skipped_) {
     st_.combine = "skipped-over-budget";
   } else if (t_.combine_ != CombineOp::kNone) {

@@ -87,7 +87,7 @@ void DirectProg::index_landed(int k, std::unique_lock<std::mutex>& lk) {
          dp.fetched[(size_t)k][(size_t)dp.indexed[(size_t)k]]) {
     dp.indexing[(size_t)k] = 1;
     const int q = dp.indexed[(size_t)k];
-    const int64_t limit = cap * (q + 1) / dp.P;
+    const int64_t limit = std::min(cap * (q + 1) / dp.P, dp.body[(size_t)k]);
     lk.unlock();
     std::vector<int64_t> c;
     std::vector<std::string> kk;

@@ -36,6 +36,8 @@ struct ProgFetch {
   std::vector<std::shared_ptr<MofFetcher>> f;
   std::vector<uint8_t*> dst, dev;
   std::vector<int64_t> cap;
+  std::vector<int64_t> body;  // cap less the partition's IFile checksum trailer (uda/ifile.h), if it has one
+  std::vector<int> id;        // the merge's name for the partition's map output
   std::vector<std::vector<int64_t>> landed;  // [phase][run]: end of the bytes that phase fetched
   std::vector<int> done;                     // per phase: partitions whose phase is fetched and queued to HBM
   std::mutex mu;
@@ -70,6 +72,7 @@ struct DirectProg {
   std::vector<std::shared_ptr<MofFetcher>> f;
   std::vector<uint8_t*> dst;
   std::vector<int64_t> cap;
+  std::vector<int64_t> body;  // cap less the partition's IFile checksum trailer: the bytes that are indexed
   std::vector<std::vector<char>> fetched;  // [k][p]
   std::vector<int> indexed;                // [k]: phases of run k indexed
   std::vector<char> indexing;              // [k]: a thread is indexing run k

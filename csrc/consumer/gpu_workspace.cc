@@ -1,5 +1,7 @@
 #include "gpu_workspace.h"
 
+#include "uda/ifile.h"
+
 namespace uda {
 
 const int kOutSlots = [] {
@@ -36,10 +38,44 @@ std::atomic<int>& staged_merges(int device) {
   return n[device & 63];
 }
 
+std::vector<uint8_t> host_decode_partition(Codec codec, const uint8_t* p, int64_t n, int* tail) {
+  *tail = 0;
+  BlockDecoder dec(codec);
+  std::vector<uint8_t> raw, buf(1 << 20);
+  auto drain = [&] {
+    for (size_t k; (k = dec.read(buf.data(), buf.size())) > 0;) raw.insert(raw.end(), buf.begin(), buf.begin() + (long)k);
+  };
+  // all but the last four bytes first: if the blocks end there, those four are the IFile checksum
+  const int64_t hold = n >= kIFileChecksumBytes ? kIFileChecksumBytes : 0;
+  dec.feed(p, (size_t)(n - hold));
+  drain();
+  if (hold && dec.idle()) {
+    *tail = kIFileChecksumBytes;
+    return raw;
+  }
+  dec.feed(p + (n - hold), (size_t)hold);
+  drain();
+  if (!dec.idle()) throw UdaError("truncated compressed partition");
+  return raw;
+}
+
 DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_runs, Codec codec, KeyKind kind,
                             int64_t spacing, hipStream_t s, const gpu::GenericMerger::RoundFn& on_round,
-                            bool pinned_src, CombineOp combine, int64_t round_bytes) {
+                            bool pinned_src, CombineOp combine, int64_t round_bytes, const ChecksumPolicy* ck) {
   double round_ms = 0;
+  DeviceMergeOut res;
+  const bool verify = ck && ck->verify;
+  auto name_of = [&](const Span& sp) {
+    return ck && ck->map_ids && sp.id >= 0 && (size_t)sp.id < ck->map_ids->size() ? (*ck->map_ids)[(size_t)sp.id]
+                                                                                   : std::string("?");
+  };
+  std::vector<gpu::DeviceChecksum::Item> items;
+  auto verified = [&] {  // the launch's results are in
+    res.checksum_parts += ws.checksum.partitions();
+    res.checksum_bytes += ws.checksum.bytes();
+    res.checksum_ms += ws.checksum.ms();
+    ws.checksum.reset();
+  };
   gpu::GenericMerger::RoundFn timed;
   if (on_round)
     timed = [&](const std::vector<int64_t>& cuts, int64_t records, bool last) {
@@ -64,13 +100,25 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
       total += sp.len;
     }
     DeviceWorkspace::ensure(ws.out, total);
+    // IFile checksums where the staged bytes are (the stager copied every partition whole: its trailer
+    // lies behind its body); the merge hands records over as it goes, so the result is read first
+    for (const Span& sp : in_runs) {
+      if (!sp.tail) continue;
+      ++res.trailers;
+      if (verify) items.push_back(gpu::DeviceChecksum::Item{sp.dev, sp.len, name_of(sp), false, 0});
+    }
+    if (!items.empty()) {
+      ws.checksum.reset();
+      ws.checksum.launch(std::move(items), s);
+      ws.checksum.finish(s, false);
+      verified();
+    }
     auto t1 = std::chrono::steady_clock::now();
     ws.h2d_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
     gpu::GenericMergeResult r =
         ws.merger.merge(runs, lens, (int)kind, ws.out.as<uint8_t>(), total, spacing, s, timed, round_bytes, combine);
     HIP_CHECK(hipStreamSynchronize(s));
     ws.device_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count() - round_ms;
-    DeviceMergeOut res;
     res.bytes = r.bytes;
     res.cuts = std::move(r.cuts);
     res.records = r.records;
@@ -80,16 +128,33 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
   gpu::BlockPlan plan;
   bool decode_on_device = false;
   std::vector<std::vector<uint8_t>> host_raw;  // host-decoded fallback
+  std::vector<int> tails(ptrs.size(), 0);  // IFile checksum trailer of run i: bytes behind its body
+  auto check_raw_len = [&](size_t i, int64_t decoded) {
+    if (tails[i] && in_runs[i].raw_len > 0 && decoded != in_runs[i].raw_len)
+      throw UdaError("compressed map output " + name_of(in_runs[i]) + " decodes to " + std::to_string(decoded) +
+                     " bytes, its index says " + std::to_string(in_runs[i].raw_len));
+  };
   if (codec != Codec::kNone) {
-    decode_on_device = gpu::plan_block_streams(codec, ptrs, lens, &plan);
+    decode_on_device = gpu::plan_block_streams(codec, ptrs, lens, &plan, &tails);
+    if (decode_on_device)
+      for (size_t i = 0; i < ptrs.size(); ++i) check_raw_len(i, plan.raw_offset[i + 1] - plan.raw_offset[i]);
     if (!decode_on_device) {
       UDA_LOG(kInfo, "device decode: framing needs a host decode (multi-chunk %s block)", codec_name(codec));
       for (size_t i = 0; i < ptrs.size(); ++i) {
-        BlockDecoder dec(codec);
-        dec.feed(ptrs[i], (size_t)lens[i]);
-        std::vector<uint8_t> raw, buf(1 << 20);
-        for (size_t n; (n = dec.read(buf.data(), buf.size())) > 0;) raw.insert(raw.end(), buf.begin(), buf.begin() + (long)n);
-        if (!dec.idle()) throw UdaError("truncated compressed partition");
+        // (the bytes are decoded here, on the host: so is their checksum)
+        std::vector<uint8_t> raw = host_decode_partition(codec, ptrs[i], lens[i], &tails[i]);
+        check_raw_len(i, (int64_t)raw.size());
+        if (tails[i]) {
+          ++res.trailers;
+          const int64_t body = lens[i] - tails[i];
+          if (verify) {
+            const uint32_t stored = ifile_stored_checksum(ptrs[i] + body), got = crc32_ieee(ptrs[i], (size_t)body);
+            if (stored != got) throw UdaError(ifile_checksum_mismatch(name_of(in_runs[i]), stored, got, body));
+            ++res.checksum_parts;
+            res.checksum_bytes += body;
+          }
+          tails[i] = 0;  // (done with: what is staged below is the decoded partition)
+        }
         host_raw.push_back(std::move(raw));
       }
       ptrs.clear();
@@ -139,15 +204,31 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
       runs.push_back(in.as<uint8_t>() + off);
       bytes.push_back(lens[i]);
     }
+    // the partition's bytes as fetched, where they were just staged; the stored value from the host copy
+    const int tail = codec != Codec::kNone ? tails[i] : (host_raw.empty() ? in_runs[i].tail : 0);
+    if (tail) {
+      ++res.trailers;
+      const int64_t body = codec != Codec::kNone ? lens[i] - tail : lens[i];
+      if (verify)
+        items.push_back(gpu::DeviceChecksum::Item{stage + off, body, name_of(in_runs[i]), true,
+                                                  ifile_stored_checksum(ptrs[i] + body)});
+    }
     off += lens[i];
   }
   if (h2d) gpu::SdmaEngine::wait(ws.h2d_sig);
+  if (!items.empty()) {  // behind the copies on s (SDMA copies have landed), ahead of the wait for them
+    ws.checksum.reset();
+    ws.checksum.launch(std::move(items), s);
+  }
   HIP_CHECK(hipStreamSynchronize(s));
+  if (ws.checksum.pending()) {
+    ws.checksum.finish(s, true);
+    verified();
+  }
   auto t1 = std::chrono::steady_clock::now();
   ws.h2d_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
   const int64_t tm = trace::host_enabled() ? trace::now_ns() : 0;
   if (tm) trace::host_event("dm_h2d", staged, (int64_t)ptrs.size(), tm - (int64_t)((t1 - t0).count()), tm);
-  DeviceMergeOut res;
   if (decode_on_device) {
     ws.decoder.decode(codec, plan, ws.packed.as<uint8_t>(), in.as<uint8_t>(), s);
     res.decoded_blocks = (int64_t)plan.descs.size();

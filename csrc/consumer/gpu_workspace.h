@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../gpu/block_decoder.h"
+#include "../gpu/device_checksum.h"
 #include "../gpu/device_ptr.h"
 #include "../gpu/generic_merger.h"
 #include "../gpu/generic_rounds.h"
@@ -38,6 +39,9 @@ struct DeviceMergeOut {
   int64_t records = 0;
   int64_t records_in = 0;      // records merged (== records without a combiner)
   int64_t decoded_blocks = 0;
+  // IFile checksum trailers (uda/ifile.h) found on the merge's runs and stripped; of those, verified
+  int64_t trailers = 0, checksum_parts = 0, checksum_bytes = 0;
+  double checksum_ms = 0;  // the device CRC, from launch to its result being read
 };
 
 constexpr int64_t kPieceBytes = 64 << 20;  // D2H piece of the pinned double buffer (hipMemcpy fallback)
@@ -61,6 +65,7 @@ struct DeviceWorkspace {
   gpu::PinnedBuffer ring;          // 2 x kPieceBytes, D2H staging of merged output
   gpu::GenericRoundsWs rounds;     // key-range round planner scratch (device fetch, generic keys)
   gpu::DeviceBuffer frame_scratch, frame_descs; // device framing walk of compressed partitions (device fetch)
+  gpu::DeviceChecksum checksum;    // IFile checksum of the task's partitions (mapred.uda.ifile.checksum)
   hipEvent_t piece_ev[2] = {nullptr, nullptr};
   // SDMA delivery ring of stream_out: kOutSlots pieces of kOutPiece bytes on the GPU's NUMA node, each
   // with its completion signal
@@ -95,6 +100,7 @@ struct DeviceWorkspace {
   void reset_stats() {
     h2d_ms = device_ms = d2h_ms = sink_ms = 0;
     out_ways = 1;
+    checksum.reset();
   }
   // D2H stream of streamed deliveries (the merge stream is busy with the next round)
   hipStream_t copy_stream() {
@@ -109,7 +115,7 @@ struct DeviceWorkspace {
   int64_t device_bytes() const {
     return (int64_t)(in.held() + out.held() + packed.held() + out2.held() + fetched.held() + frame_scratch.held() +
                      frame_descs.held()) +
-           merger.workspace_bytes();
+           merger.workspace_bytes() + checksum.device_bytes();
   }
 };
 
@@ -126,7 +132,22 @@ struct Span {
   const uint8_t* p;
   int64_t len;
   const uint8_t* dev = nullptr;  // device copy staged while the fetch went on (EarlyStager)
+  // A fetched partition's IFile checksum (uda/ifile.h). Uncompressed: `tail` trailer bytes lie behind the
+  // `len` body bytes, at p and at dev. Compressed: len counts the whole partition and the framing walk
+  // finds the trailer; raw_len > 0 is what the body must decode to. id: index into ChecksumPolicy::map_ids.
+  int tail = 0;
+  int64_t raw_len = 0;
+  int id = -1;
 };
+
+// device_merge verifies the trailers of its runs (verify) or only strips them; null: strips them
+struct ChecksumPolicy {
+  bool verify = true;
+  const std::vector<std::string>* map_ids = nullptr;  // for the mismatch message
+};
+// Host decode of one compressed partition whose framing the device cannot resolve. *tail = 4 when the
+// blocks end four bytes ahead of the partition's end: those are its IFile checksum and are not decoded.
+std::vector<uint8_t> host_decode_partition(Codec codec, const uint8_t* p, int64_t n, int* tail);
 
 // Stages fetched partitions to HBM as soon as each one is complete in pinned memory, so the H2D
 // copies overlap the remaining fetches (one issuing thread, one copy stream: the round-1 attempt
@@ -537,7 +558,8 @@ struct GateLease {
 DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_runs, Codec codec, KeyKind kind,
                             int64_t spacing, hipStream_t s, const gpu::GenericMerger::RoundFn& on_round = nullptr,
                             bool pinned_src = false, CombineOp combine = CombineOp::kNone,
-                            int64_t round_bytes = 256ll << 20);  // on_round's rounds (mapred.uda.gpu.merge.round.bytes)
+                            int64_t round_bytes = 256ll << 20,  // on_round's rounds (mapred.uda.gpu.merge.round.bytes)
+                            const ChecksumPolicy* ck = nullptr);
 
 // piece boundaries (in cut indices) of a merged output: pieces of up to `limit` bytes ending on record
 // boundaries; empty if a single cut interval is larger than `limit`

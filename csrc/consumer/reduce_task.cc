@@ -72,6 +72,7 @@ MofFetcher::MofFetcher(ReduceTask* task, FetchParams p, int64_t buf_size, Codec 
   proto_.map_id = p_.map_id;
   proto_.reduce_id = p_.reduce_id;
   if (codec_ != Codec::kNone) dec_ = std::make_unique<BlockDecoder>(codec_);
+  verify_ = task_->checksum_ == ChecksumMode::kAuto;
 }
 
 void MofFetcher::start() {
@@ -114,6 +115,7 @@ void MofFetcher::on_done(int b, const FetchAck& a) {
       len_[b] = a.sent;
       ready_[b] = true;
       part_len_ = a.part_len;
+      raw_len_ = a.raw_len;
       proto_.mof_offset = a.mof_offset;
       proto_.raw_len = a.raw_len;
       proto_.part_len = a.part_len;
@@ -257,19 +259,109 @@ void MofFetcher::release_pair() {
   task_->cv_.notify_all();
 }
 
+void MofFetcher::take_trailer(const uint8_t* p, int64_t n) {
+  for (int64_t i = 0; i < n && stored_n_ < kIFileChecksumBytes; ++i) stored_[stored_n_++] = p[i];
+}
+
+void MofFetcher::check_trailer() {
+  const int64_t body = part_len_ - kIFileChecksumBytes;
+  if (stored_n_ != kIFileChecksumBytes) throw UdaError("IFile checksum trailer of " + p_.map_id + " is incomplete");
+  if (!verify_) {
+    task_->note_checksum(0, 0);
+    return;
+  }
+  const uint32_t stored = ifile_stored_checksum(stored_);
+  if (stored != crc_) throw UdaError(ifile_checksum_mismatch(p_.map_id, stored, crc_, body));
+  task_->note_checksum(1, body);
+}
+
+int64_t MofFetcher::pull_body(uint8_t* dst, int64_t cap) {
+  const int64_t n = pull_raw(dst, cap);
+  if (n == 0) return 0;
+  if (trailer_ < 0) trailer_ = ifile_trailer_bytes(raw_len_, part_len_);
+  if (!trailer_) return n;  // no trailer: the bytes as they come
+  const int64_t body = part_len_ - trailer_, start = seen_;
+  seen_ += n;
+  const int64_t keep = std::clamp<int64_t>(body - start, 0, n);
+  if (verify_ && keep > 0) crc_ = crc32_ieee(dst, (size_t)keep, crc_);
+  take_trailer(dst + keep, n - keep);
+  if (seen_ >= body) {
+    // the trailer may lie in a chunk of its own, which a consumer that stops at the EOF marker never asks
+    // for: take it now, so the body's last bytes are handed out verified and the buffer pair goes back
+    if (tmp_.empty()) tmp_.resize((size_t)buf_size_);
+    while (seen_ < part_len_) {
+      const int64_t m = pull_raw(tmp_.data(), (int64_t)tmp_.size());
+      if (m == 0) break;
+      seen_ += m;
+      take_trailer(tmp_.data(), m);
+    }
+    check_trailer();
+  }
+  return keep;
+}
+
 int64_t MofFetcher::pull(uint8_t* dst, int64_t cap) {
-  if (!dec_) return pull_raw(dst, cap);
-  std::vector<uint8_t> tmp;
+  if (!dec_) return pull_body(dst, cap);
   for (;;) {
-    size_t r = dec_->read(dst, (size_t)cap);
-    if (r > 0) return (int64_t)r;
-    if (tmp.empty()) tmp.resize((size_t)buf_size_);
-    int64_t n = pull_raw(tmp.data(), (int64_t)tmp.size());
-    if (n == 0) {
+    const size_t r = dec_->read(dst, (size_t)cap);
+    if (r > 0) {
+      decoded_ += (int64_t)r;
+      // all but the held-back bytes are fed by the time the decoder hands out its last bytes (below): the
+      // trailer is checked before the consumer sees the EOF marker and stops reading
+      if (!tail_decided_ && seen_ >= part_len_ && dec_->idle()) {
+        tail_decided_ = true;
+        if (raw_len_ > 0 && decoded_ != raw_len_)
+          throw UdaError("compressed map output " + p_.map_id + " decodes to " + std::to_string(decoded_) +
+                         " bytes, its index says " + std::to_string(raw_len_));
+        check_trailer();
+      }
+      return (int64_t)r;
+    }
+    if (part_len_ >= 0 && seen_ >= part_len_) {  // every byte of the partition is in
+      if (!tail_decided_) {
+        tail_decided_ = true;
+        if (dec_->idle()) {  // (a partition of nothing but a trailer)
+          check_trailer();
+          return 0;
+        }
+        dec_->feed(stored_, (size_t)stored_n_);  // not at a block boundary: a stream without a trailer
+        continue;
+      }
       if (!dec_->idle()) throw UdaError("compressed MOF ended inside a block");
       return 0;
     }
-    dec_->feed(tmp.data(), (size_t)n);
+    if (tmp_.empty()) tmp_.resize((size_t)buf_size_);
+    for (;;) {
+      const int64_t n = pull_raw(tmp_.data(), (int64_t)tmp_.size());
+      if (n == 0) {
+        if (part_len_ < 0 || seen_ < part_len_) throw UdaError("compressed MOF " + p_.map_id + " ended early");
+        break;
+      }
+      // the partition's last four bytes are held back: the checksum if the blocks end ahead of them
+      const int64_t hold = part_len_ >= kIFileChecksumBytes ? kIFileChecksumBytes : 0;
+      if (hold == 0) tail_decided_ = true;
+      const int64_t body = part_len_ - hold, start = seen_;
+      seen_ += n;
+      const int64_t keep = std::clamp<int64_t>(body - start, 0, n);
+      if (keep > 0) {
+        if (verify_) crc_ = crc32_ieee(tmp_.data(), (size_t)keep, crc_);
+        dec_->feed(tmp_.data(), (size_t)keep);
+      }
+      take_trailer(tmp_.data() + keep, n - keep);
+      if (seen_ < body || seen_ >= part_len_) break;  // (the held-back bytes come with the ones before them)
+    }
+  }
+}
+
+void ReduceTask::note_checksum(int64_t parts, int64_t bytes, double gpu_ms) {
+  std::lock_guard<std::mutex> g(st_mu_);
+  if (parts > 0) {
+    st_.ifile_checksum = "verified";
+    st_.checksum_partitions += parts;
+    st_.checksum_bytes += bytes;
+    st_.gpu_checksum_ms += gpu_ms;
+  } else if (st_.ifile_checksum == "none") {
+    st_.ifile_checksum = "off";
   }
 }
 
@@ -456,6 +548,10 @@ void ReduceTask::on_init(const InitParams& p_in) {
   if (cob != "skip" && cob != "combine")
     throw ProtocolError("unknown mapred.uda.merge.combine.over.budget \"" + cob + "\" (skip or combine)");
   combine_over_budget_ = cob == "combine";
+  // IFile checksum trailers (uda/ifile.h): detected and stripped either way; auto verifies them
+  const std::string ck = host_->get_conf("mapred.uda.ifile.checksum", "auto");
+  if (!checksum_mode_from_conf(ck, &checksum_))
+    throw ProtocolError("unknown mapred.uda.ifile.checksum \"" + ck + "\" (auto or off)");
   // key-range rounds in which one device merge hands its output over (GenericMerger::merge's round_bytes)
   merge_round_bytes_ = std::max<int64_t>(4 << 10, host_->conf_i64("mapred.uda.gpu.merge.round.bytes", 256ll << 20));
   if (backend_ == "gpu") {
@@ -1006,6 +1102,8 @@ std::string ReduceTask::stats_json() const {
     << ",\"hbm_reserved\":" << s.hbm_reserved << ",\"round_bytes\":" << s.round_bytes << ",\"gpu_device\":" << s.gpu_device << ",\"merge_path\":\"" << s.merge_path << "\""
     << ",\"combine\":\"" << s.combine << "\",\"combine_in_records\":" << s.combine_in_records
     << ",\"combine_groups\":" << s.combine_groups << ",\"merge_rounds\":" << s.merge_rounds
+    << ",\"ifile_checksum\":\"" << s.ifile_checksum << "\",\"checksum_partitions\":" << s.checksum_partitions
+    << ",\"checksum_bytes\":" << s.checksum_bytes << ",\"gpu_checksum_ms\":" << s.gpu_checksum_ms
     << ",\"finished\":" << (finished_ ? "true" : "false") << "}";
   return o.str();
 }

@@ -98,6 +98,12 @@ struct ReduceStats {
   std::string combine = "none";
   int64_t combine_in_records = 0, combine_groups = 0;
   int64_t merge_rounds = 0;     // GPU: hand-overs of device merges' output (rounds of mapred.uda.gpu.merge.round.bytes)
+  // mapred.uda.ifile.checksum (uda/ifile.h): "none" (no partition carried a trailer), "verified", "off"
+  // (trailers stripped, not verified) or "skipped-over-budget" (the GPU hybrid stripped them unverified);
+  // partitions and body bytes verified; wall time of the device CRC from launch to its result being read
+  std::string ifile_checksum = "none";
+  int64_t checksum_partitions = 0, checksum_bytes = 0;
+  double gpu_checksum_ms = 0;
   std::string backend;
 };
 
@@ -207,6 +213,10 @@ class ReduceTask {
   double hbm_budget_conf_ = 0;
   int delivery_pack_ = 2;                       // mapred.uda.gpu.delivery.pack: colpack version, 0 = off
   CombineOp combine_ = CombineOp::kNone;        // mapred.uda.merge.combine
+  ChecksumMode checksum_ = ChecksumMode::kAuto;  // mapred.uda.ifile.checksum
+  // IFile trailers were detected and stripped: `parts` partitions of `bytes` body bytes verified (by the
+  // host as they were pulled, or by the device in `gpu_ms`), or, with parts == 0, left unverified (off)
+  void note_checksum(int64_t parts, int64_t bytes, double gpu_ms = 0);
   bool combine_over_budget_ = false;            // mapred.uda.merge.combine.over.budget = combine (default skip)
   int64_t merge_round_bytes_ = 256ll << 20;     // mapred.uda.gpu.merge.round.bytes: a device merge's hand-over rounds
   int64_t delivery_piece_bytes_ = 64ll << 20;   // mapred.uda.gpu.delivery.piece.bytes
@@ -286,9 +296,27 @@ class MofFetcher : public std::enable_shared_from_this<MofFetcher> {
   bool first_arrived() const { return first_done_; }
   const FetchParams& params() const { return p_; }
   int64_t part_len() const { return part_len_; }
+  int64_t raw_len() const { return raw_len_; }  // the index's rawLength (as part_len: once first_arrived())
   int64_t wait_ns = 0;
 
  private:
+  // IFile checksum trailer (uda/ifile.h). Uncompressed: the answer's lengths tell whether the partition
+  // has one; pull() then hands out the body only, keeps a running CRC of it and compares it with the
+  // trailer before the body's last bytes are returned (the consumer stops reading at the EOF marker).
+  // Compressed: the decoder is fed all but the partition's last four bytes; if it then stands at a
+  // block boundary those four are the checksum, else they are fed too (a stream without one).
+  int64_t pull_body(uint8_t* dst, int64_t cap);
+  void take_trailer(const uint8_t* p, int64_t n);
+  void check_trailer();
+  int trailer_ = -1;        // uncompressed: 0 / 4 once the first answer is in
+  bool verify_ = true;
+  int64_t seen_ = 0;        // partition bytes pulled so far
+  uint32_t crc_ = 0;        // of the body bytes seen
+  uint8_t stored_[4] = {0, 0, 0, 0};
+  int stored_n_ = 0;
+  bool tail_decided_ = false;   // compressed: the last four bytes were taken as trailer or fed
+  int64_t decoded_ = 0;         // compressed: raw bytes handed out
+  std::vector<uint8_t> tmp_;
   // Prepare a fetch into buffer `buf` (mu_ held); the returned call runs after mu_ is released
   // because a transport may complete inline.
   std::function<void()> prepare(int buf);
@@ -309,6 +337,7 @@ class MofFetcher : public std::enable_shared_from_this<MofFetcher> {
   int64_t requested_ = 0;   // next offset to request
   int64_t consumed_ = 0;
   int64_t part_len_ = -1;
+  int64_t raw_len_ = -1;
   FetchRequest proto_;
   bool first_done_ = false;
   std::string error_;

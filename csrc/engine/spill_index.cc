@@ -12,22 +12,7 @@
 
 namespace uda {
 
-uint32_t crc32_ieee(const uint8_t* p, size_t n, uint32_t crc) {
-  static uint32_t table[256];
-  static const bool init = [] {
-    for (uint32_t i = 0; i < 256; ++i) {
-      uint32_t c = i;
-      for (int k = 0; k < 8; ++k) c = (c & 1) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-      table[i] = c;
-    }
-    return true;
-  }();
-  (void)init;
-  crc = ~crc;
-  for (size_t i = 0; i < n; ++i) crc = table[(crc ^ p[i]) & 0xFF] ^ (crc >> 8);
-  return ~crc;
-}
-
+// (crc32_ieee lives in ifile_checksum.cc)
 namespace {
 void put_be64(uint8_t* d, int64_t v) {
   for (int i = 7; i >= 0; --i) {

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "uda/error.h"
+#include "uda/ifile.h"
 #include "uda/trace.h"
 
 namespace uda {
@@ -18,15 +19,20 @@ uint32_t be32(const uint8_t* p) {
 }  // namespace
 
 bool plan_block_streams(Codec codec, const std::vector<const uint8_t*>& ptrs, const std::vector<int64_t>& lens,
-                        BlockPlan* plan) {
+                        BlockPlan* plan, std::vector<int>* tails) {
   plan->descs.clear();
   plan->raw_offset.assign(1, 0);
+  if (tails) tails->assign(lens.size(), 0);
   int64_t in_base = 0, raw = 0;
   for (size_t s = 0; s < lens.size(); ++s) {
     const uint8_t* p = ptrs[s];
     const int64_t n = lens[s];
     int64_t i = 0;
     while (i < n) {
+      if (tails && n - i == kIFileChecksumBytes) {  // exactly four bytes at a block boundary: the IFile checksum
+        (*tails)[s] = kIFileChecksumBytes;
+        break;
+      }
       if (i + 4 > n) return false;
       const int64_t block_raw = be32(p + i);
       i += 4;
@@ -60,14 +66,16 @@ bool plan_block_streams(Codec codec, const std::vector<const uint8_t*>& ptrs, co
 }
 
 bool plan_block_streams_device(Codec codec, const std::vector<const uint8_t*>& dptrs, const std::vector<int64_t>& lens,
-                               BlockPlan* plan, DeviceBuffer& scratch, DeviceBuffer& desc_scratch, hipStream_t s) {
+                               BlockPlan* plan, DeviceBuffer& scratch, DeviceBuffer& desc_scratch, hipStream_t s,
+                               std::vector<int>* tails, const std::function<void(const std::vector<int>&)>& on_tails) {
   const int n = (int)dptrs.size();
   plan->descs.clear();
   plan->raw_offset.assign(1, 0);
   plan->raw_total = 0;
+  if (tails) tails->assign((size_t)n, 0);
   if (n == 0) return true;
-  // scratch: ptrs | lens | desc_first | raw_first | nblocks | raw (8 B each per stream) | status (4 B)
-  const size_t tb = (size_t)n * 52 + 64;
+  // scratch: ptrs | lens | desc_first | raw_first | nblocks | raw (8 B each per stream) | status, tails (4 B)
+  const size_t tb = (size_t)n * 56 + 64;
   if (scratch.size() < tb) scratch.alloc(tb + tb / 2);
   auto* d_ptrs = scratch.as<const uint8_t*>();
   auto* d_lens = reinterpret_cast<int64_t*>(d_ptrs + n);
@@ -78,16 +86,19 @@ bool plan_block_streams_device(Codec codec, const std::vector<const uint8_t*>& d
   int* d_status = reinterpret_cast<int*>(d_raw + n);
   HIP_CHECK(hipMemcpyAsync(d_ptrs, dptrs.data(), 8 * (size_t)n, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(d_lens, lens.data(), 8 * (size_t)n, hipMemcpyHostToDevice, s));
+  int* d_tails = tails ? d_status + n : nullptr;
   HIP_CHECK(hipMemsetAsync(d_status, 0, 4 * (size_t)n, s));
-  launch_frame_streams(d_ptrs, d_lens, n, (int)codec, nullptr, nullptr, d_nb, d_raw, nullptr, d_status, s);
+  launch_frame_streams(d_ptrs, d_lens, n, (int)codec, nullptr, nullptr, d_nb, d_raw, nullptr, d_status, s, d_tails);
   std::vector<int64_t> nb((size_t)n), raw((size_t)n);
   std::vector<int> st((size_t)n);
   HIP_CHECK(hipMemcpyAsync(nb.data(), d_nb, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipMemcpyAsync(raw.data(), d_raw, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipMemcpyAsync(st.data(), d_status, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
+  if (tails) HIP_CHECK(hipMemcpyAsync(tails->data(), d_tails, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   for (int i = 0; i < n; ++i)
     if (st[(size_t)i]) return false;
+  if (tails && on_tails) on_tails(*tails);
   std::vector<int64_t> dfirst((size_t)n), rfirst((size_t)n);
   int64_t nd = 0, rt = 0;
   for (int i = 0; i < n; ++i) {
@@ -106,7 +117,7 @@ bool plan_block_streams_device(Codec codec, const std::vector<const uint8_t*>& d
   HIP_CHECK(hipMemcpyAsync(d_dfirst, dfirst.data(), 8 * (size_t)n, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(d_rfirst, rfirst.data(), 8 * (size_t)n, hipMemcpyHostToDevice, s));
   launch_frame_streams(d_ptrs, d_lens, n, (int)codec, d_dfirst, d_rfirst, d_nb, d_raw, d_descs.as<DecodeDesc>(),
-                       d_status, s);
+                       d_status, s, d_tails);
   HIP_CHECK(hipMemcpyAsync(plan->descs.data(), d_descs.as(), (size_t)nd * sizeof(DecodeDesc), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   return true;

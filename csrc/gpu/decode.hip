@@ -981,14 +981,19 @@ bool lzo_lane_decode_host(const uint8_t* in, int64_t n, uint8_t* out, int64_t ou
 // framing is not resolvable without decoding (the host planner's `false`).
 __global__ void __launch_bounds__(64) frame_streams_kernel(const uint8_t* const* ptrs, const int64_t* lens, int nstreams,
                                                            int codec, const int64_t* desc_first, const int64_t* raw_first,
-                                                           int64_t* nblocks, int64_t* raw, DecodeDesc* out, int* status) {
+                                                           int64_t* nblocks, int64_t* raw, DecodeDesc* out, int* status,
+                                                           int* tails) {
   const int sidx = blockIdx.x * blockDim.x + threadIdx.x;
   if (sidx >= nstreams) return;
   const uint8_t* p = ptrs[sidx];
   const int64_t n = lens[sidx];
   int64_t i = 0, blocks = 0, rsum = 0;
-  int bad = 0;
+  int bad = 0, tail = 0;
   while (i < n && !bad) {
+    if (tails && n - i == 4) {  // exactly four bytes at a block boundary: the IFile checksum (uda/ifile.h)
+      tail = 4;
+      break;
+    }
     if (i + 4 > n) {
       bad = 1;
       break;
@@ -1046,16 +1051,17 @@ __global__ void __launch_bounds__(64) frame_streams_kernel(const uint8_t* const*
   if (!out) {
     nblocks[sidx] = blocks;
     raw[sidx] = rsum;
+    if (tails) tails[sidx] = tail;
   }
   if (bad) status[sidx] = 1;
 }
 
 void launch_frame_streams(const uint8_t* const* ptrs, const int64_t* lens, int nstreams, int codec,
                           const int64_t* desc_first, const int64_t* raw_first, int64_t* nblocks, int64_t* raw,
-                          DecodeDesc* out, int* status, hipStream_t s) {
+                          DecodeDesc* out, int* status, hipStream_t s, int* tails) {
   if (nstreams <= 0) return;
   hipLaunchKernelGGL(frame_streams_kernel, dim3((unsigned)((nstreams + 63) / 64)), dim3(64), 0, s, ptrs, lens, nstreams,
-                     codec, desc_first, raw_first, nblocks, raw, out, status);
+                     codec, desc_first, raw_first, nblocks, raw, out, status, tails);
 }
 
 void launch_block_decode(int codec, const uint8_t* in, uint8_t* out, const DecodeDesc* descs, int n, int* status,

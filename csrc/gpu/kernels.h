@@ -310,9 +310,34 @@ bool lzo_lane_decode_host(const uint8_t* in, int64_t n, uint8_t* out, int64_t ou
 // Framing walk of device-resident streams (one lane per stream). out == nullptr: per-stream block
 // counts and raw bytes; else the descriptors with absolute src addresses (decode with in = nullptr).
 // status[s] = 1: framing not resolvable without decoding (zero status first).
+// tails (device, nstreams ints; optional): the walk accepts an IFile checksum trailer, as plan_block_streams
+// does (block_decoder.h): tails[s] = 4 when exactly four bytes remain at a block boundary, else 0 (written
+// by the counting pass). Null: the walk that knows no trailer.
 void launch_frame_streams(const uint8_t* const* ptrs, const int64_t* lens, int nstreams, int codec,
                           const int64_t* desc_first, const int64_t* raw_first, int64_t* nblocks, int64_t* raw,
-                          DecodeDesc* out, int* status, hipStream_t s);
+                          DecodeDesc* out, int* status, hipStream_t s, int* tails = nullptr);
+
+// ---------------------------------------------------------------- CRC32 of device-resident byte ranges
+// zlib's crc32() of n byte ranges in one batched launch (crc32.hip): the IFile checksum of fetched
+// partitions (uda/ifile.h). A range is cut into chunks of crc32_chunk_bytes() at 16-byte-aligned
+// addresses: range i has chunks(i) = ceil((((uintptr_t)p & 15) + len) / chunk) of them (0 for len 0), and
+// chunk_first[i] is the sum of chunks(j) for j < i (chunk_first[n] = total_chunks), as crc32_chunk_plan
+// computes. One wave computes a chunk's CRC state with coalesced 16-byte loads; a second kernel folds a
+// range's chunk states in order, one wave per range. No atomics: the result does not depend on scheduling.
+// out[i] = zlib.crc32(bytes of range i) for any len >= 0 and any alignment of p. Never allocates, never
+// synchronizes; ws: crc32_ws_bytes(total_chunks) device bytes.
+struct CrcDesc {
+  const uint8_t* p;
+  int64_t len;
+};
+int64_t crc32_chunk_bytes();
+size_t crc32_ws_bytes(int64_t total_chunks);
+// chunk_first (n + 1 entries) of host-known descriptors; returns total_chunks
+int64_t crc32_chunk_plan(const CrcDesc* descs, int n, int64_t* chunk_first);
+void launch_crc32(const CrcDesc* descs, int n, const int64_t* chunk_first, int64_t total_chunks, void* ws,
+                  uint32_t* out, hipStream_t s);
+// stored[i] = the big-endian int in the four bytes after range i (its IFile trailer)
+void launch_crc32_trailers(const CrcDesc* descs, int n, uint32_t* stored, hipStream_t s);
 
 // ---------------------------------------------------------------- validation
 // Checks key order of `n` FIXED10 records at `recs` (and against *prev_key if has_prev) and

@@ -185,6 +185,31 @@ uint64_t ifile_checksum(const uint8_t* p, size_t n, int64_t* records, int64_t* b
 void write_spill_index(const std::string& path, const std::vector<int64_t>& index);
 // false (why set) if the file is missing, short or fails its checksum
 bool read_spill_index(const std::string& path, std::vector<int64_t>* index, std::string* why);
+
+// ----------------------------------------------------------------------------- IFile checksum trailer
+// Hadoop's IFile.Writer writes through an IFileOutputStream, which appends the CRC32 of the partition's
+// bytes as they lie on disk (compressed or not) as a big-endian int. The index's partLength counts
+// those four bytes, rawLength (decoded record bytes, EOF marker included) does not. The value is the
+// zlib / IEEE CRC32 (reflected, polynomial 0xEDB88320) of [start, start + partLength - 4).
+// Beyond the reference, which stopped at the EOF marker and verified nothing (engine/ifile_checksum.cc).
+constexpr int kIFileChecksumBytes = 4;
+// zlib's crc32(): `crc` is the CRC of the bytes before p (0 for none). Slice-by-8.
 uint32_t crc32_ieee(const uint8_t* p, size_t n, uint32_t crc = 0);
+// zlib's crc32_combine(): the CRC of A || B from crc(A), crc(B) and len(B), i.e. crc_a times
+// x^(8 * len_b) modulo the polynomial, plus crc_b.
+uint32_t crc32_combine(uint32_t crc_a, uint32_t crc_b, int64_t len_b);
+// Trailer bytes (0 or kIFileChecksumBytes) of an UNCOMPRESSED partition from the lengths its index
+// gives: part_len == raw_len + 4 has one; part_len == raw_len, a raw_len <= 0 (an answer that does not
+// say) and anything else have none. A compressed partition's lengths cannot tell: the framing walk
+// decides (gpu/block_decoder.h, MofFetcher): exactly 4 bytes left at a block boundary are the checksum.
+int ifile_trailer_bytes(int64_t raw_len, int64_t part_len);
+// The stored value: a big-endian int at `trailer`.
+uint32_t ifile_stored_checksum(const uint8_t* trailer);
+// "IFile checksum mismatch in map output <map id>: stored 0x%08x, computed 0x%08x over <n> bytes"
+std::string ifile_checksum_mismatch(const std::string& map_id, uint32_t stored, uint32_t computed, int64_t n);
+// mapred.uda.ifile.checksum: "auto" (a detected trailer is stripped and verified) or "off" (stripped,
+// not verified). false for any other value.
+enum class ChecksumMode { kAuto, kOff };
+bool checksum_mode_from_conf(const std::string& v, ChecksumMode* mode);
 
 }  // namespace uda

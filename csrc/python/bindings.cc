@@ -15,6 +15,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstring>
+#include <random>
 
 #include "block_decoder.h"
 #include "device_engine.h"
@@ -698,6 +699,134 @@ PYBIND11_MODULE(_uda_native, m) {
     if (!d.idle()) throw py::value_error("truncated block stream");
     return py::bytes(out);
   });
+
+  // ---- IFile checksum trailer (uda/ifile.h)
+  m.def("crc32", [](py::bytes b, uint32_t seed) {
+    std::string s = b;
+    return crc32_ieee((const uint8_t*)s.data(), s.size(), seed);
+  }, py::arg("data"), py::arg("seed") = 0);
+  m.def("crc32_combine", [](uint32_t a, uint32_t b, int64_t len_b) { return crc32_combine(a, b, len_b); },
+        py::arg("crc_a"), py::arg("crc_b"), py::arg("len_b"));
+  m.def("ifile_trailer_bytes", &ifile_trailer_bytes, py::arg("raw_len"), py::arg("part_len"));
+  // the trailer-aware host framing walk of one block-compressed stream: (blocks, tail bytes)
+  m.def("plan_block_streams", [](int codec, py::bytes b) {
+    std::string s = b;
+    gpu::BlockPlan plan;
+    std::vector<int> tails;
+    if (!gpu::plan_block_streams((Codec)codec, {(const uint8_t*)s.data()}, {(int64_t)s.size()}, &plan, &tails))
+      throw py::value_error("block framing malformed or not resolvable without decoding");
+    return py::make_tuple((int64_t)plan.descs.size(), tails[0]);
+  }, py::arg("codec"), py::arg("stream"));
+  m.def("gpu_crc32_chunk_bytes", [] { return gpu::crc32_chunk_bytes(); });
+  // zlib.crc32 of every input by one launch of the device kernels (crc32.hip): the inputs lie in one device
+  // buffer, each at an address that is `misalign` modulo 16
+  m.def("gpu_crc32", [](const std::vector<std::string>& inputs, int misalign, int device) {
+    if (misalign < 0 || misalign > 15) throw py::value_error("misalign must be 0..15");
+    const int n = (int)inputs.size();
+    std::vector<uint32_t> out((size_t)n, 0);
+    if (n == 0) return out;
+    py::gil_scoped_release rel;
+    HIP_CHECK(hipSetDevice(device));
+    std::vector<int64_t> at((size_t)n);
+    int64_t total = 16;
+    for (int i = 0; i < n; ++i) {
+      at[(size_t)i] = total + misalign;
+      total = (total + misalign + (int64_t)inputs[(size_t)i].size() + 15) & ~(int64_t)15;
+    }
+    gpu::DeviceBuffer data((size_t)total + 16);
+    uint8_t* base = data.as<uint8_t>();
+    if ((uintptr_t)base & 15) throw UdaError("device allocation is not 16-byte aligned");
+    hipStream_t s;
+    HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    std::vector<gpu::CrcDesc> descs((size_t)n);
+    std::vector<int64_t> first((size_t)n + 1);
+    for (int i = 0; i < n; ++i) {
+      const std::string& in = inputs[(size_t)i];
+      descs[(size_t)i] = gpu::CrcDesc{base + at[(size_t)i], (int64_t)in.size()};
+      if (!in.empty()) HIP_CHECK(hipMemcpyAsync(base + at[(size_t)i], in.data(), in.size(), hipMemcpyHostToDevice, s));
+    }
+    const int64_t chunks = gpu::crc32_chunk_plan(descs.data(), n, first.data());
+    gpu::DeviceBuffer d_descs((size_t)n * sizeof(gpu::CrcDesc)), d_first(((size_t)n + 1) * 8), d_out((size_t)n * 4),
+        ws(gpu::crc32_ws_bytes(chunks));
+    HIP_CHECK(hipMemcpyAsync(d_descs.as(), descs.data(), (size_t)n * sizeof(gpu::CrcDesc), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(d_first.as(), first.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
+    gpu::launch_crc32(d_descs.as<gpu::CrcDesc>(), n, d_first.as<int64_t>(), chunks, ws.as(), d_out.as<uint32_t>(), s);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(out.data(), d_out.as(), (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(hipStreamDestroy(s));
+    return out;
+  }, py::arg("inputs"), py::arg("misalign") = 0, py::arg("device") = 0);
+  // benchmarks/run_configs.py checksum: `parts` ranges of `part_bytes` random bytes; per repetition the
+  // milliseconds (hipEvents) of the CRC launch and of launch_batched_copy of the same bytes
+  m.def("gpu_crc32_bench", [](int parts, int64_t part_bytes, int warmup, int reps, int device) {
+    std::vector<double> crc_ms, copy_ms;
+    bool ok = true;
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      const int64_t stride = (part_bytes + 255) & ~(int64_t)255;
+      gpu::DeviceBuffer src((size_t)(stride * parts) + 16), dst((size_t)(stride * parts) + 16);
+      hipStream_t s;
+      HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      {  // random bytes (a pattern repeated: the kernel's speed does not depend on the values)
+        std::vector<uint8_t> pat(64 << 20);
+        std::mt19937_64 rng(7);
+        for (size_t i = 0; i + 8 <= pat.size(); i += 8) {
+          const uint64_t v = rng();
+          std::memcpy(&pat[i], &v, 8);
+        }
+        for (int64_t o = 0; o < stride * parts; o += (int64_t)pat.size())
+          HIP_CHECK(hipMemcpyAsync(src.as<uint8_t>() + o, pat.data(), (size_t)std::min<int64_t>((int64_t)pat.size(), stride * parts - o),
+                                   hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+      }
+      std::vector<gpu::CrcDesc> descs((size_t)parts);
+      std::vector<gpu::CopyDesc> copies((size_t)parts);
+      std::vector<int64_t> first((size_t)parts + 1);
+      for (int i = 0; i < parts; ++i) {
+        descs[(size_t)i] = gpu::CrcDesc{src.as<uint8_t>() + stride * i, part_bytes};
+        copies[(size_t)i] = gpu::CopyDesc{src.as<uint8_t>() + stride * i, dst.as<uint8_t>() + stride * i, part_bytes};
+      }
+      const int64_t chunks = gpu::crc32_chunk_plan(descs.data(), parts, first.data());
+      gpu::DeviceBuffer d_descs((size_t)parts * sizeof(gpu::CrcDesc)), d_first(((size_t)parts + 1) * 8),
+          d_out((size_t)parts * 4), ws(gpu::crc32_ws_bytes(chunks)), d_copies((size_t)parts * sizeof(gpu::CopyDesc));
+      HIP_CHECK(hipMemcpyAsync(d_descs.as(), descs.data(), (size_t)parts * sizeof(gpu::CrcDesc), hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(d_first.as(), first.data(), ((size_t)parts + 1) * 8, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(d_copies.as(), copies.data(), (size_t)parts * sizeof(gpu::CopyDesc), hipMemcpyHostToDevice, s));
+      hipEvent_t e0, e1;
+      HIP_CHECK(hipEventCreate(&e0));
+      HIP_CHECK(hipEventCreate(&e1));
+      std::vector<uint32_t> got((size_t)parts), ref;
+      for (int which = 0; which < 2; ++which)
+        for (int r = 0; r < warmup + reps; ++r) {
+          HIP_CHECK(hipEventRecord(e0, s));
+          if (which == 0)
+            gpu::launch_crc32(d_descs.as<gpu::CrcDesc>(), parts, d_first.as<int64_t>(), chunks, ws.as(), d_out.as<uint32_t>(), s);
+          else
+            gpu::launch_batched_copy(d_copies.as<gpu::CopyDesc>(), parts, part_bytes, s);
+          HIP_CHECK(hipEventRecord(e1, s));
+          HIP_CHECK(hipEventSynchronize(e1));
+          float ms = 0;
+          HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+          if (r >= warmup) (which == 0 ? crc_ms : copy_ms).push_back((double)ms);
+          if (which == 0) {  // every repetition gives the same values
+            HIP_CHECK(hipMemcpy(got.data(), d_out.as(), (size_t)parts * 4, hipMemcpyDeviceToHost));
+            if (ref.empty()) ref = got;
+            ok = ok && got == ref;
+          }
+        }
+      (void)hipEventDestroy(e0);
+      (void)hipEventDestroy(e1);
+      HIP_CHECK(hipStreamDestroy(s));
+    }
+    py::dict d;
+    d["crc_ms"] = crc_ms;
+    d["copy_ms"] = copy_ms;
+    d["bytes"] = (int64_t)parts * part_bytes;
+    d["repeatable"] = ok;
+    return d;
+  }, py::arg("parts"), py::arg("part_bytes"), py::arg("warmup") = 3, py::arg("reps") = 10, py::arg("device") = 0);
 
   m.def("generate_runs", [](const std::string& kind, int maps, int reducers, int64_t rows, uint64_t seed) {
     std::vector<std::vector<std::vector<uint8_t>>> r;

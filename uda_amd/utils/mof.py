@@ -22,13 +22,19 @@ CODEC_CLASSES = {
 }
 
 
-def encode_partitions(partitions: list[bytes], codec: str | None = None, block_size: int = 256 * 1024):
-    """Returns (file_bytes, index) with index = [(start, raw_len, part_len)]."""
+def encode_partitions(partitions: list[bytes], codec: str | None = None, block_size: int = 256 * 1024,
+                      checksum: bool = False):
+    """Returns (file_bytes, index) with index = [(start, raw_len, part_len)].
+
+    checksum: end every partition the way Hadoop's IFile.Writer does, with the CRC32 of its bytes as
+    written (compressed or not) as a big-endian int; part_len counts those four bytes, raw_len does not."""
     data = bytearray()
     index = []
     for p in partitions:
         raw = len(p)
         body = native().block_compress(CODECS[codec], p, block_size) if codec else p
+        if checksum:
+            body = bytes(body) + struct.pack(">I", zlib.crc32(body) & 0xFFFFFFFF)
         index.append((len(data), raw, len(body)))
         data += body
     return bytes(data), index
@@ -51,11 +57,11 @@ def read_index(path: str):
 
 
 def write_mof(directory: str, map_id: str, partitions: list[bytes], codec: str | None = None,
-              block_size: int = 256 * 1024) -> tuple[str, list]:
+              block_size: int = 256 * 1024, checksum: bool = False) -> tuple[str, list]:
     """Write <directory>/<map_id>/file.out(+.index). Returns (file.out path, index)."""
     d = os.path.join(directory, map_id)
     os.makedirs(d, exist_ok=True)
-    data, index = encode_partitions(partitions, codec, block_size)
+    data, index = encode_partitions(partitions, codec, block_size, checksum)
     out = os.path.join(d, "file.out")
     with open(out, "wb") as f:
         f.write(data)
