@@ -11,6 +11,7 @@
 // in merged order gives every record its output offset; a wave copies 64 records at a time with
 // all lanes on each record (byte-granular, records are not aligned).
 #include <cstdlib>
+#include "generic_cmp.h"
 #include "kernels.h"
 #include "uda/compare.h"
 #include "uda/vint.h"
@@ -583,7 +584,7 @@ __global__ void __launch_bounds__(256) normalize_kernel(GenericKeyCtx ctx, const
   // one unaligned 8-byte load when the content has 8 bytes (the byte loop costs 8 load instructions)
   typedef uint64_t __attribute__((aligned(1))) u64_u;
   e.hi = cl >= 8 ? __builtin_bswap64(*reinterpret_cast<const u64_u*>(key + o)) : load_be_prefix(key + o, cl);
-  const uint64_t capped = cl > 0xFFFF ? 0xFFFF : (uint64_t)cl;
+  const uint64_t capped = cl > kGenLenCap ? (uint64_t)kGenLenCap : (uint64_t)cl;
   e.lo = (capped << 48) | (uint64_t)g;
   out[g] = e;
   ctx.keyptr[g] = key + o;
@@ -827,6 +828,9 @@ size_t f1_parallel_workspace(int64_t nchunks, int64_t nsup) {
          (size_t)nchunks * (kF1Chase * 3 + 1) * 4 + 256;
 }
 int64_t f1_super_chunks() { return kF1Super; }
+int f1_halo_bytes() { return kF1Halo; }
+int f1_entries() { return kF1Entries; }
+int f1_chase_survivors() { return kF1Chase; }
 
 void launch_f1_parallel(uint8_t* const* bases, const int64_t* nbytes, int nruns, const int64_t* chunk_base,
                         const int32_t* chunk_run, int64_t nchunks, const int64_t* sup_base, const int32_t* sup_run,

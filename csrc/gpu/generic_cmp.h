@@ -8,6 +8,8 @@ namespace uda {
 namespace gpu {
 
 constexpr uint64_t kGenOrdMask = 0xFFFFFFFFFFFFull;
+constexpr int kGenLenCap = 0xFFFF;      // the length field of Elem.lo saturates here
+constexpr int kGenStagedKeyBytes = 24;  // key bytes after the common prefix that both merge kernels stage in LDS
 
 // Big-endian 8 bytes of p (zero padded past n bytes).
 __device__ __forceinline__ uint64_t load_be8(const uint8_t* p, int n) {

@@ -283,11 +283,11 @@ __global__ void __launch_bounds__(kGkThreads) gk_cell_kernel(GenericKeyCtx ctx, 
     if (w1[x] != w1[y]) return w1[x] < w1[y];
     if (w2[x] != w2[y]) return w2[x] < w2[y];
     const int lx = klen[x], ly = klen[y];
-    if (lx > P + 24 && ly > P + 24) {
+    if (lx > P + kGenStagedKeyBytes && ly > P + kGenStagedKeyBytes) {
       const uint8_t* px = ctx.keyptr[E[x].lo & kGenOrdMask];
       const uint8_t* py = ctx.keyptr[E[y].lo & kGenOrdMask];
       const int m = lx < ly ? lx : ly;
-      for (int i = P + 24; i < m; i += 8) {
+      for (int i = P + kGenStagedKeyBytes; i < m; i += 8) {
         const uint64_t a = load_be8(px + i, m - i), b = load_be8(py + i, m - i);
         if (a != b) return a < b;
       }
@@ -355,7 +355,11 @@ __global__ void __launch_bounds__(kGkThreads) gk_cell_kernel(GenericKeyCtx ctx, 
 
 }  // namespace
 
+static_assert(kGenStagedKeyBytes == 24, "w0, w1, w2 hold three 8-byte words");
+
 int generic_kway_cap() { return kGkCap; }
+int generic_staged_key_bytes() { return kGenStagedKeyBytes; }
+int generic_len_cap() { return kGenLenCap; }
 
 void launch_gk_sample(const Elem* cur, const int64_t* eoff, const int64_t* soff, int K, int64_t step, int64_t ns,
                       Elem* out, hipStream_t s) {

@@ -127,6 +127,8 @@ void launch_merge_pass_generic(const Elem* in, Elem* out, PassDesc pd, const int
 // ---------------------------------------------------------------- single-pass K-way merge, generic keys
 constexpr int kGkMaxRuns = 128;  // runs per merge on the generic single-pass path
 int generic_kway_cap();          // elements per cell
+int generic_staged_key_bytes();  // key bytes after the common prefix staged in LDS by both generic merge kernels
+int generic_len_cap();           // where the length field of a GENERIC Elem.lo saturates
 // samples[soff[r] + j] = cur[eoff[r] + j * step + step / 2]
 void launch_gk_sample(const Elem* cur, const int64_t* eoff, const int64_t* soff, int K, int64_t step, int64_t ns,
                       Elem* out, hipStream_t s);
@@ -189,6 +191,9 @@ void launch_f1_scan(uint8_t* const* bases, const int64_t* nbytes, int nruns, con
 // run r's superchunks, sup_run their run. status[r] == 2: the run needs the serial scan.
 size_t f1_parallel_workspace(int64_t nchunks, int64_t nsup);
 int64_t f1_super_chunks();
+int f1_halo_bytes();       // bytes of the next chunk staged behind a chunk
+int f1_entries();          // entry offsets tabulated per chunk; a longer straddling record goes serial
+int f1_chase_survivors();  // most surviving chains per chunk handed to the chase kernel
 void launch_f1_parallel(uint8_t* const* bases, const int64_t* nbytes, int nruns, const int64_t* chunk_base,
                         const int32_t* chunk_run, int64_t nchunks, const int64_t* sup_base, const int32_t* sup_run,
                         int64_t nsup, void* workspace, int64_t* ck_start, int64_t* ck_count, int64_t* counts,

@@ -224,6 +224,7 @@ __global__ void __launch_bounds__(kThreads) merge_pass_kernel(const Elem* in, El
 // the same total order as GenericCmp (used by the partition kernel).
 constexpr int kGenItems = kGenericMergeTile / kThreads;  // 4
 constexpr uint64_t kOrdMask = kGenOrdMask;
+static_assert(kGenStagedKeyBytes == 24, "w0, w1, w2 hold three 8-byte words");
 
 __global__ void __launch_bounds__(kThreads) merge_pass_generic_lds_kernel(const Elem* in, Elem* out, PassDesc pd,
                                                                           const int64_t* splits, GenericKeyCtx ctx) {
@@ -285,11 +286,11 @@ __global__ void __launch_bounds__(kThreads) merge_pass_generic_lds_kernel(const 
     if (w1[x] != w1[y]) return w1[x] < w1[y];
     if (w2[x] != w2[y]) return w2[x] < w2[y];
     const int lx = klen[x], ly = klen[y];
-    if (lx > P + 24 && ly > P + 24) {
+    if (lx > P + kGenStagedKeyBytes && ly > P + kGenStagedKeyBytes) {
       const uint8_t* px = ctx.keyptr[lds[x].lo & kOrdMask];
       const uint8_t* py = ctx.keyptr[lds[y].lo & kOrdMask];
       const int n = lx < ly ? lx : ly;
-      for (int i = P + 24; i < n; i += 8) {
+      for (int i = P + kGenStagedKeyBytes; i < n; i += 8) {
         const uint64_t a = load_be8(px + i, n - i), b = load_be8(py + i, n - i);
         if (a != b) return a < b;
       }

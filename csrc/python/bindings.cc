@@ -1647,6 +1647,22 @@ PYBIND11_MODULE(_uda_native, m) {
     d["links"] = links;
     return d;
   });
+  // The constants of the generic merge kernels (F1 index, K-way cells, pairwise tiles, key compare), for
+  // tests that place their inputs on those boundaries. Plain numbers: callable without a device.
+  m.def("gpu_generic_geometry", [] {
+    py::dict d;
+    d["f1_chunk"] = gpu::f1_chunk_bytes();
+    d["f1_halo"] = gpu::f1_halo_bytes();
+    d["f1_entries"] = gpu::f1_entries();
+    d["f1_super_chunks"] = gpu::f1_super_chunks();
+    d["f1_chase"] = gpu::f1_chase_survivors();
+    d["gk_cap"] = gpu::generic_kway_cap();
+    d["gk_max_runs"] = gpu::kGkMaxRuns;
+    d["generic_tile"] = gpu::kGenericMergeTile;
+    d["staged_key_bytes"] = gpu::generic_staged_key_bytes();
+    d["len_cap"] = gpu::generic_len_cap();
+    return d;
+  });
   // Merge IFile runs (any bytes-like objects, read in place) on the device. Returns
   // (merged bytes, buffer cuts, records, merge passes, device merge ms, runs indexed serially, records merged).
   // combine: "none" or an op of uda/combine.h (sum.int, sum.long, min.int, max.int, min.long, max.long,
