@@ -95,7 +95,7 @@ size_t snappy_compress(const uint8_t* src, size_t n, uint8_t* dst) {
 bool snappy_uncompressed_length(const uint8_t* src, size_t n, size_t* out) {
   size_t v = 0;
   int shift = 0;
-  for (size_t i = 0; i < n && i < 10; ++i) {
+  for (size_t i = 0; i < n && i < 5; ++i) {  // a varint32: libsnappy refuses a sixth byte
     v |= (size_t)(src[i] & 0x7F) << shift;
     if (!(src[i] & 0x80)) {
       *out = v;
@@ -112,7 +112,7 @@ bool snappy_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, s
     size_t v = 0;
     int shift = 0;
     bool ok = false;
-    while (ip < n && ip < 10) {
+    while (ip < n && ip < 5) {  // a varint32: libsnappy refuses a sixth byte
       uint8_t b = src[ip++];
       v |= (size_t)(b & 0x7F) << shift;
       if (!(b & 0x80)) {

@@ -28,7 +28,13 @@ namespace gpu {
 namespace {
 
 constexpr int kWavesPerBlock = 4;
-constexpr int kWin = 2048;  // per-wave LDS window of compressed input
+constexpr int kWin = 2048;      // per-wave LDS window of compressed input, based at ip & ~(kWinAlign - 1)
+constexpr int kWinAlign = 16;
+constexpr int kRegAlign = 4;    // the register window (kRegWin below) is based at ip & ~(kRegAlign - 1)
+constexpr int kShortCopy = 64;  // lean parse: a copy of up to one byte per lane is a single masked move
+constexpr int kVecBytes = 16;   // wave_copy: bytes per lane and step, kWaveStep per wave
+constexpr int kWaveStep = 64 * kVecBytes;
+constexpr int kLaneWord = 8;    // lane-per-block parse: input bytes per register refill
 
 struct Wave {
   const uint8_t* in;
@@ -64,7 +70,7 @@ __device__ __forceinline__ bool ensure(Wave& w, int64_t ip, int need) {
   if (ip + need > w.in_end) return false;
   if (ip >= w.win_base && ip + need <= w.win_end) return true;
   if (R) {
-    const int64_t base = ip & ~(int64_t)3;
+    const int64_t base = ip & ~(int64_t)(kRegAlign - 1);
     const int64_t end = min(base + kRegWin, w.in_end);
     const int64_t p = base + 4 * w.lane;
     uint32_t v = 0;
@@ -80,7 +86,7 @@ __device__ __forceinline__ bool ensure(Wave& w, int64_t ip, int need) {
     return true;
   }
   wave_sync();
-  const int64_t base = ip & ~(int64_t)15;
+  const int64_t base = ip & ~(int64_t)(kWinAlign - 1);
   const int64_t end = min(base + kWin, w.in_end);
   for (int i = w.lane * 16; i < kWin; i += 64 * 16) {
     const int64_t p = base + i;
@@ -121,8 +127,8 @@ struct __attribute__((packed, aligned(1))) U128 {
 
 // Non-overlapping copy dst[0, len) = src[0, len) by the 64 lanes.
 __device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, int64_t len, int lane) {
-  const int64_t nv = len & ~(int64_t)15;
-  for (int64_t i = (int64_t)lane * 16; i < nv; i += 64 * 16)
+  const int64_t nv = len & ~(int64_t)(kVecBytes - 1);
+  for (int64_t i = (int64_t)lane * kVecBytes; i < nv; i += kWaveStep)
     *reinterpret_cast<U128*>(dst + i) = *reinterpret_cast<const U128*>(src + i);
   for (int64_t i = nv + lane; i < len; i += 64) dst[i] = src[i];
 }
@@ -157,7 +163,7 @@ __device__ bool snappy_chunk(Wave& w, int64_t ip, int64_t cend, int64_t op, int6
   int64_t ulen = 0;
   int shift = 0;
   for (;;) {
-    if (shift > 35 || !ensure<R>(w, ip, 1)) return false;
+    if (shift > 28 || !ensure<R>(w, ip, 1)) return false;  // a varint32 has at most 5 bytes
     const uint32_t b = byte_at<R>(w, ip++);
     ulen |= (int64_t)(b & 0x7F) << shift;
     if (!(b & 0x80)) break;
@@ -360,7 +366,7 @@ struct LeanWin {
 };
 
 __device__ __forceinline__ void lean_fill(LeanWin& w, const uint8_t* ib, uint32_t ip, uint32_t ip_end, int lane) {
-  const uint32_t base = ip & ~3u;
+  const uint32_t base = ip & ~(uint32_t)(kRegAlign - 1);
   const uint32_t end = min(base + (uint32_t)kRegWin, ip_end);
   const uint32_t p = base + 4 * (uint32_t)lane;
   uint32_t v = 0;
@@ -376,7 +382,11 @@ __device__ __forceinline__ void lean_fill(LeanWin& w, const uint8_t* ib, uint32_
   w.lim = end == ip_end ? 0xFFFFFFFFu : end;
 }
 
-// Bytes ip .. ip+3, little-endian (bytes past the chunk end read as zero).
+// Bytes ip .. ip+3, little-endian. Only the bytes below ip_end mean anything: past the chunk end the peek
+// holds zeros, or, when the chunk's last window is exactly full (its byte kRegWin - 1 is the chunk's last),
+// that window's first bytes, because the high word of lane 63 comes from lane 0. No memory past the chunk
+// is read either way, and every caller tests that a byte exists before it uses it (the LZO parse by its
+// three-byte margin, the LZ4 parse by a test per field), so what those bytes hold never matters.
 __device__ __forceinline__ uint32_t lean_peek4(LeanWin& w, const uint8_t* ib, uint32_t ip, uint32_t ip_end, int lane) {
   if (ip + 4 > w.lim) lean_fill(w, ib, ip, ip_end, lane);
   const uint32_t d = ip - w.base;
@@ -394,7 +404,7 @@ __device__ __forceinline__ void lean_literal(LeanWin& w, const uint8_t* ib, uint
     len = min(len, clip - op);
   }
   if (len == 0) return;
-  if (len <= 64) {
+  if (len <= kShortCopy) {
     if (ip + len > w.lim) lean_fill(w, ib, ip, ip_end, lane);
     const uint32_t e = ip - w.base + (uint32_t)lane;  // window offset of this lane's byte
     const uint32_t word = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(e & 0xFCu), (int)w.rw);
@@ -418,7 +428,7 @@ __device__ __forceinline__ void lean_match(uint8_t* ob, uint32_t op, uint32_t of
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     flushed = op;
   }
-  if (len <= 64) {
+  if (len <= kShortCopy) {
     if ((uint32_t)lane < len) ob[op + lane] = ob[src + (off >= len ? (uint32_t)lane : (uint32_t)lane % off)];
   } else if (off >= len) {
     wave_copy(ob + op, ob + src, len, lane);
@@ -459,11 +469,16 @@ __device__ bool lzo_lean_chunk(const uint8_t* ib, uint8_t* ob, uint32_t ip, cons
         ++ip;
         if (t == 0) {
           uint32_t b;
+          // t is compared against what is left inside the run, as lz4_lean_chunk does: a run of literals
+          // longer than the rest of the chunk is corrupt whatever follows, so t never passes
+          // ip_end - ip + 255 < 2^31 + 255, and neither t + 18 nor the sums ip + t + 3 and op + t of the
+          // test below (ip, op < 2^31) can wrap 32 bits however many zero bytes the chunk holds
           for (;;) {
             if (ip >= ip_end) return false;
             b = lean_peek4(w, ib, ip, ip_end, lane) & 0xFF;
             if (b != 0) break;
             t += 255;
+            if (t > ip_end - ip) return false;
             ++ip;
           }
           t += 15 + b;
@@ -504,11 +519,14 @@ __device__ bool lzo_lean_chunk(const uint8_t* ib, uint8_t* ob, uint32_t ip, cons
       if (t == 2) {  // zero-run length extension
         ++ip;
         uint32_t b;
+        // as on the literal side: a match longer than the output left (op <= oend here) is corrupt, so
+        // t stays below 2^31 + 255 and op + t of the test after the token cannot wrap
         for (;;) {
           if (ip + 3 > ip_end) return false;  // this byte and the two offset bytes after the run
           b = lean_peek4(w, ib, ip, ip_end, lane) & 0xFF;
           if (b != 0) break;
           t += 255;
+          if (t > oend - op) return false;
           ++ip;
         }
         t += lmask + b;
@@ -590,7 +608,7 @@ __global__ void __launch_bounds__(64 * kWavesPerBlock)
 //   match-length extension; the chunk ends right after a literal run.
 // Same window, literal and match helpers as the LZO lean kernel. Unlike LZO1X the stream has no end
 // marker, so nothing about a token's bytes is implied by the previous check: the token needs ip < ip_end,
-// the offset ip + 2 <= ip_end, every extension byte its own test. lean_peek4 reads zeros past the chunk
+// the offset ip + 2 <= ip_end, every extension byte its own test. lean_peek4 reads no memory past the chunk
 // end, so a peek is always safe to take; its bytes are only used after the test that says they exist.
 // Lengths are compared against what is left (len > oend - op), and inside the extension runs, so a long
 // run of 0xFF neither wraps a 32-bit length nor parses further than the chunk could use.
@@ -755,17 +773,17 @@ struct __attribute__((packed, aligned(1))) U64p {
 struct LaneIn {  // the next input bytes of one lane, 8 at a time
   const uint8_t* in;
   int64_t end;     // one past the last readable byte of this block
-  int64_t base = -8;
+  int64_t base = -kLaneWord;
   uint64_t word = 0;
   __host__ __device__ __forceinline__ uint32_t at(int64_t ip) {
     const int64_t d = ip - base;
-    if (d < 0 || d >= 8) {
+    if (d < 0 || d >= kLaneWord) {
       base = ip;
-      if (ip + 8 <= end) {
+      if (ip + kLaneWord <= end) {
         word = reinterpret_cast<const U64p*>(in + ip)->v;
       } else {
         word = 0;
-        for (int k = 0; k < 8 && ip + k < end; ++k) word |= (uint64_t)in[ip + k] << (8 * k);
+        for (int k = 0; k < kLaneWord && ip + k < end; ++k) word |= (uint64_t)in[ip + k] << (8 * k);
       }
       return (uint32_t)(word & 0xFF);
     }
@@ -781,7 +799,7 @@ __host__ __device__ __forceinline__ void lane_copy(uint8_t* dst, const uint8_t* 
 }
 
 __host__ __device__ __forceinline__ void lane_match(uint8_t* out, int64_t op, int64_t off, int64_t len) {
-  if (off >= 8) {
+  if (off >= kLaneWord) {
     lane_copy(out + op, out + op - off, len);
   } else {
     for (int64_t i = 0; i < len; ++i) out[op + i] = out[op - off + i];
@@ -1062,6 +1080,13 @@ void launch_frame_streams(const uint8_t* const* ptrs, const int64_t* lens, int n
   if (nstreams <= 0) return;
   hipLaunchKernelGGL(frame_streams_kernel, dim3((unsigned)((nstreams + 63) / 64)), dim3(64), 0, s, ptrs, lens, nstreams,
                      codec, desc_first, raw_first, nblocks, raw, out, status, tails);
+}
+
+DecodeGeometry decode_geometry() {
+  static_assert(kLaneWord == (int)sizeof(U64p) && kVecBytes == (int)sizeof(U128) && kRegWin == 64 * kRegAlign,
+                "decode geometry");
+  return DecodeGeometry{kRegWin,   kRegAlign,  kWin,      kWinAlign,      kShortCopy,
+                        kVecBytes, kWaveStep, kLaneWord, kWavesPerBlock, (int)kDecodePrefixSlot};
 }
 
 void launch_block_decode(int codec, const uint8_t* in, uint8_t* out, const DecodeDesc* descs, int n, int* status,

@@ -681,7 +681,7 @@ DeviceReduceStats device_reduce_fixed_blocks(const DeviceReduceConfig& cfg, int 
   }
   auto R = [&](int64_t b, int k) { return plan.descs[(size_t)b].dst - raw0[k]; };  // block's raw offset in its stream
   // ---- prefix pass: the block first-key index
-  constexpr int64_t kSlot = 128;  // >= 103 bytes to the first record start + 13 bytes of record head and key
+  constexpr int64_t kSlot = kDecodePrefixSlot;  // 128 >= 103 bytes to the first record start + 13 bytes of record head and key
   WsLease lease(cfg.device, N * kTeraRecordBytes);
   FixedWs& ws = *lease.w;
   hipStream_t s = ws.s;

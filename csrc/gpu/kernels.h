@@ -310,6 +310,18 @@ struct DecodeDesc {
 // clip > 0: prefix decode, only the first `clip` raw bytes of every block are produced (at its dst).
 void launch_block_decode(int codec, const uint8_t* in, uint8_t* out, const DecodeDesc* descs, int n, int* status,
                          hipStream_t s, int64_t clip = 0);
+// The slot of a prefix decode that only wants each block's first record key (device_reduce.cc): block b's
+// first kDecodePrefixSlot bytes land at b * kDecodePrefixSlot.
+constexpr int64_t kDecodePrefixSlot = 128;
+// The constants of the decode kernels, for tests that place tokens on their boundaries: the register and
+// LDS input windows and the alignment of their bases, the longest copy done as one masked byte move per
+// lane, wave_copy's bytes per lane and per wave step, the lane parse's input word, the blocks (waves) per
+// workgroup, and the prefix slot above.
+struct DecodeGeometry {
+  int reg_window, reg_align, lds_window, lds_align, short_copy, vec_bytes, wave_step, lane_word, waves_per_block,
+      prefix_slot;
+};
+DecodeGeometry decode_geometry();
 // The LZO lane kernel's per-block decode on the host (tests without a GPU).
 bool lzo_lane_decode_host(const uint8_t* in, int64_t n, uint8_t* out, int64_t out_cap, int64_t* out_len);
 // Framing walk of device-resident streams (one lane per stream). out == nullptr: per-stream block

@@ -1857,8 +1857,30 @@ PYBIND11_MODULE(_uda_native, m) {
     }
     return py::make_tuple(out, (double)ms);
   }, py::arg("records"), py::arg("device") = 0, py::arg("staged") = false);
-  // F6: decode Hadoop block-compressed streams on the device; returns (raw streams, blocks, decode_ms)
-  m.def("gpu_block_decode", [](const std::string& codec_cls, const std::vector<std::string>& streams, int device) {
+  // The constants of the block decode kernels (kernels.h: DecodeGeometry), for tests that place tokens on
+  // their boundaries. Plain numbers: callable without a device.
+  m.def("gpu_decode_geometry", [] {
+    const gpu::DecodeGeometry g = gpu::decode_geometry();
+    py::dict d;
+    d["reg_window"] = g.reg_window;
+    d["reg_align"] = g.reg_align;
+    d["lds_window"] = g.lds_window;
+    d["lds_align"] = g.lds_align;
+    d["short_copy"] = g.short_copy;
+    d["vec_bytes"] = g.vec_bytes;
+    d["wave_step"] = g.wave_step;
+    d["lane_word"] = g.lane_word;
+    d["waves_per_block"] = g.waves_per_block;
+    d["prefix_slot"] = g.prefix_slot;
+    return d;
+  });
+  // F6: decode Hadoop block-compressed streams on the device; returns (raw streams, blocks, decode_ms).
+  // clip > 0: the prefix decode as device_reduce.cc lays it out, block b's first min(clip, raw) bytes at
+  // b * clip of a buffer of blocks * clip bytes plus a 256-byte guard, every byte 0xA5 before the launch;
+  // returns (the whole buffer, blocks, decode_ms). The full decode's output buffer is filled the same way, so
+  // a byte a kernel failed to write never shows what an earlier launch left at that address.
+  m.def("gpu_block_decode", [](const std::string& codec_cls, const std::vector<std::string>& streams, int device,
+                               int64_t clip) {
     bool unsup = false;
     Codec c = codec_from_class(codec_cls, &unsup);
     if (c == Codec::kNone)
@@ -1867,7 +1889,10 @@ PYBIND11_MODULE(_uda_native, m) {
           : codec_cls == "lz4"  ? Codec::kLz4
                                 : Codec::kNone;
     if (c == Codec::kNone) throw py::value_error("unknown codec " + codec_cls);
+    if (clip < 0) throw py::value_error("clip < 0");
+    constexpr int64_t kGuard = 256;
     std::vector<std::string> outs;
+    std::string whole;
     int64_t blocks = 0;
     double ms = 0;
     {
@@ -1883,7 +1908,9 @@ PYBIND11_MODULE(_uda_native, m) {
       }
       gpu::BlockPlan plan;
       if (!gpu::plan_block_streams(c, ptrs, lens, &plan)) throw UdaError("block framing not resolvable on device");
-      gpu::DeviceBuffer din((size_t)std::max<int64_t>(staged, 16)), dout((size_t)std::max<int64_t>(plan.raw_total, 16));
+      const int64_t nb = (int64_t)plan.descs.size();
+      const int64_t out_bytes = clip > 0 ? nb * clip + kGuard : plan.raw_total;
+      gpu::DeviceBuffer din((size_t)std::max<int64_t>(staged, 16)), dout((size_t)std::max<int64_t>(out_bytes, 16));
       hipStream_t s;
       HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
       int64_t off = 0;
@@ -1891,23 +1918,49 @@ PYBIND11_MODULE(_uda_native, m) {
         if (!st.empty()) HIP_CHECK(hipMemcpyAsync(din.as<uint8_t>() + off, st.data(), st.size(), hipMemcpyHostToDevice, s));
         off += (int64_t)st.size();
       }
+      if (out_bytes) HIP_CHECK(hipMemsetAsync(dout.as(), 0xA5, (size_t)out_bytes, s));
       HIP_CHECK(hipStreamSynchronize(s));
-      gpu::DeviceBlockDecoder dec;
-      auto t0 = std::chrono::steady_clock::now();
-      dec.decode(c, plan, din.as<uint8_t>(), dout.as<uint8_t>(), s);
-      ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-      std::string all((size_t)plan.raw_total, '\0');
-      if (plan.raw_total) HIP_CHECK(hipMemcpyAsync(&all[0], dout.as(), all.size(), hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-      HIP_CHECK(hipStreamDestroy(s));
-      for (size_t i = 0; i < streams.size(); ++i)
-        outs.push_back(all.substr((size_t)plan.raw_offset[i], (size_t)(plan.raw_offset[i + 1] - plan.raw_offset[i])));
-      blocks = (int64_t)plan.descs.size();
+      if (clip > 0) {
+        std::vector<gpu::DecodeDesc> pd(plan.descs);
+        for (int64_t b = 0; b < nb; ++b) pd[(size_t)b].dst = b * clip;
+        gpu::DeviceBuffer ddesc((size_t)std::max<int64_t>(nb, 1) * sizeof(gpu::DecodeDesc)), dstat(sizeof(int));
+        int st = 0;
+        const size_t desc_bytes = (size_t)nb * sizeof(gpu::DecodeDesc);
+        if (nb) HIP_CHECK(hipMemcpyAsync(ddesc.as(), pd.data(), desc_bytes, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemsetAsync(dstat.as(), 0, sizeof(int), s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        auto t0 = std::chrono::steady_clock::now();
+        gpu::launch_block_decode((int)c, din.as<uint8_t>(), dout.as<uint8_t>(), ddesc.as<gpu::DecodeDesc>(), (int)nb,
+                                 dstat.as<int>(), s, clip);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(&st, dstat.as(), sizeof(int), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        whole.assign((size_t)out_bytes, '\0');
+        HIP_CHECK(hipMemcpyAsync(&whole[0], dout.as(), whole.size(), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipStreamDestroy(s));
+        if (st) throw UdaError(std::string("corrupt ") + codec_name(c) + " block (device prefix decode)");
+        blocks = nb;
+      } else {
+        gpu::DeviceBlockDecoder dec;
+        auto t0 = std::chrono::steady_clock::now();
+        dec.decode(c, plan, din.as<uint8_t>(), dout.as<uint8_t>(), s);
+        ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        std::string all((size_t)plan.raw_total, '\0');
+        if (plan.raw_total) HIP_CHECK(hipMemcpyAsync(&all[0], dout.as(), all.size(), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipStreamDestroy(s));
+        for (size_t i = 0; i < streams.size(); ++i)
+          outs.push_back(all.substr((size_t)plan.raw_offset[i], (size_t)(plan.raw_offset[i + 1] - plan.raw_offset[i])));
+        blocks = (int64_t)plan.descs.size();
+      }
     }
+    if (clip > 0) return py::make_tuple(py::object(py::bytes(whole)), blocks, ms);
     py::list l;
     for (auto& o : outs) l.append(py::bytes(o));
-    return py::make_tuple(l, blocks, ms);
-  }, py::arg("codec"), py::arg("streams"), py::arg("device") = 0);
+    return py::make_tuple(py::object(l), blocks, ms);
+  }, py::arg("codec"), py::arg("streams"), py::arg("device") = 0, py::arg("clip") = 0);
   m.def("nccl_unique_id", []() { return py::bytes(gpu::nccl_unique_id()); });
   // RCCL data-plane self test on one GPU: communicator bootstrap from an ncclUniqueId and the grouped
   // send/recv counts exchange the shuffle plan uses (world 1: the rank exchanges with itself).

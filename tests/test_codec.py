@@ -1,10 +1,13 @@
 """In-tree Snappy / LZO1X codecs and Hadoop block framing.
 
 Snappy parity is pinned against pyarrow's Snappy (an independent implementation) in both
-directions. LZO1X: no independent LZO implementation is importable here (liblzo2 is absent), so its
-parity with liblzo2 is unpinned; it is checked by round trips through our encoder (which emits
-literal runs, M2/M3/M4 matches, long-length extensions and trailing-literal states) and by
-rejecting corrupted streams.
+directions. LZO1X: no independent LZO implementation is importable here (liblzo2 is absent), so
+parity with what liblzo2's encoder emits is unpinned. Here the decoder is checked by round trips
+through our encoder (which emits literal runs, M2/M3/M4 matches, long-length extensions and
+trailing-literal states) and by rejecting corrupted streams; the token kinds our encoder never
+emits (both M1 forms, M4 with the distance bit set by hand) and every LZO1X state transition are
+pinned by the streams assembled token by token in tests/decode_cases.py, against a pure-Python
+decoder (test_decode_cases_cpu.py on the host, test_gpu_decode_cases.py on the device).
 """
 import os
 import random
