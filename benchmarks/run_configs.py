@@ -19,6 +19,9 @@
                       VIntWritable counts), and the F4 kernels phase by phase.
                       --vocab N --tasks N --maps N: one low-duplication, few-task shape (several inner
                       rounds per task); --over-budget: the GPU hybrid, skipping against combining.
+  key_order           IntWritable keys (non-negative, so both orders deliver the same bytes), 90-byte values: the
+                      device merge under mapred.uda.key.order reference vs hadoop (the 8-byte normalized key per
+                      record that the numeric path stores and reads), the two alternated.
 
 Each prints one JSON line per result. Data is synthetic (native generators, csrc/engine/datagen.cc).
 """
@@ -697,10 +700,52 @@ def checksum(args) -> dict:
     return out
 
 
+def key_order(args) -> dict:
+    """The generic device merge of IntWritable-keyed runs under both key orders. Keys are non-negative, where
+    memcmp and the signed order agree, so the two merges must deliver the same bytes."""
+    import numpy as np
+
+    from uda_amd import ops
+    INT = "org.apache.hadoop.io.IntWritable"
+    rows = int(args.gb * 1e9 / 96 / args.maps)  # record: 2 header bytes, 4 key bytes, 90 value bytes
+    rng = np.random.default_rng(17)
+    runs = []
+    for _ in range(args.maps):
+        keys = np.sort(rng.integers(0, 1 << 31, size=rows, dtype=np.uint32))
+        rec = rng.integers(0, 256, size=(rows, 96), dtype=np.uint8)
+        rec[:, 0], rec[:, 1] = 4, 90
+        rec[:, 2:6] = keys.astype(">u4").view(np.uint8).reshape(rows, 4)
+        runs.append(rec.tobytes() + b"\xff\xff")
+    nbytes = sum(len(r) - 2 for r in runs)
+    orders = ("reference", "hadoop")
+    body = {}
+    for o in orders:  # first full-size calls: the merger's workspace, and the normalized-key buffer
+        body[o], _ = ops.merge_runs(runs, INT, "gpu", key_order=o)
+    assert body["reference"] == body["hadoop"], "the two orders differ on non-negative keys"
+    reps = max(3, args.rounds)
+    dev = {o: [] for o in orders}
+    wall = {o: [] for o in orders}
+    for _ in range(reps):
+        for o in orders:
+            t0 = time.perf_counter()
+            ops.merge_runs(runs, INT, "gpu", key_order=o)
+            wall[o].append(time.perf_counter() - t0)
+            dev[o].append(ops.last_stats["merge_ms"])
+    med = lambda v: sorted(v)[len(v) // 2]
+    out = {"config": "IntWritable keys >= 0, 90-byte values: device merge under mapred.uda.key.order reference vs hadoop",
+           "gb": round(nbytes / 1e9, 3), "runs": args.maps, "records": rows * args.maps, "reps": reps, "byte_identical": True}
+    for o in orders:
+        out[o] = {"device_merge_ms_median": round(med(dev[o]), 2), "device_merge_ms_min": round(min(dev[o]), 2),
+                  "device_merge_ms_max": round(max(dev[o]), 2), "device_merge_gbps": round(nbytes / med(dev[o]) / 1e6, 2),
+                  "s_incl_h2d_d2h_median": round(med(wall[o]), 3)}
+    out["hadoop_over_reference_device_ms"] = round(med(dev["hadoop"]) / med(dev["reference"]), 3)
+    return out
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("config", choices=["wordcount_loopback", "wordcount_tcp", "cpu_reference", "secondary_sort", "spill", "decode", "aio",
-                                       "netmerger", "radix", "hybrid_budget", "combine", "combine_kernels", "checksum"])
+                                       "netmerger", "radix", "hybrid_budget", "combine", "combine_kernels", "checksum", "key_order"])
     ap.add_argument("--dir", default="/tmp")
     ap.add_argument("--codec", default="snappy", choices=["snappy", "lzo", "lz4"])
     ap.add_argument("--gb", type=float, default=1.0)

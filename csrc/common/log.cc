@@ -146,11 +146,56 @@ KeyKind key_kind_from_class(const char* n) {
   return KeyKind::kUnsupported;
 }
 
+// Under KeyOrder::kHadoop the numeric classes get a kind of their own (key_sortable); BooleanWritable, whose
+// Hadoop comparator is a byte compare, and every other class keep the reference's kind.
+KeyKind key_kind_from_class(const char* n, KeyOrder order) {
+  if (order == KeyOrder::kHadoop && n) {
+    static const struct {
+      const char* cls;
+      KeyKind kind;
+    } numeric[] = {
+        {"org.apache.hadoop.io.ByteWritable", KeyKind::kByte},
+        {"org.apache.hadoop.io.ShortWritable", KeyKind::kShort},
+        {"org.apache.hadoop.io.IntWritable", KeyKind::kInt},
+        {"org.apache.hadoop.io.LongWritable", KeyKind::kLong},
+        {"org.apache.hadoop.io.VIntWritable", KeyKind::kVInt},
+        {"org.apache.hadoop.io.VLongWritable", KeyKind::kVLong},
+        {"org.apache.hadoop.io.FloatWritable", KeyKind::kFloat},
+        {"org.apache.hadoop.io.DoubleWritable", KeyKind::kDouble},
+    };
+    for (const auto& e : numeric)
+      if (strcmp(n, e.cls) == 0) return e.kind;
+  }
+  return key_kind_from_class(n);
+}
+
+bool key_order_from_conf(const std::string& v, KeyOrder* out) {
+  if (v == "reference") {
+    *out = KeyOrder::kReference;
+    return true;
+  }
+  if (v == "hadoop") {
+    *out = KeyOrder::kHadoop;
+    return true;
+  }
+  return false;
+}
+
+const char* key_order_name(KeyOrder o) { return o == KeyOrder::kHadoop ? "hadoop" : "reference"; }
+
 const char* key_kind_name(KeyKind k) {
   switch (k) {
     case KeyKind::kText: return "text";
     case KeyKind::kRaw: return "raw";
     case KeyKind::kBytes: return "bytes";
+    case KeyKind::kByte: return "byte";
+    case KeyKind::kShort: return "short";
+    case KeyKind::kInt: return "int";
+    case KeyKind::kLong: return "long";
+    case KeyKind::kVInt: return "vint";
+    case KeyKind::kVLong: return "vlong";
+    case KeyKind::kFloat: return "float";
+    case KeyKind::kDouble: return "double";
     default: return "unsupported";
   }
 }

@@ -760,7 +760,9 @@ bool ReduceTask::merge_gpu_device(bool probe) {
       const int64_t b = std::min(rb, total);
       // (a combiner's group index and sums: 17 B per record more, 0.27 of the bytes at 64 B records)
       const double comb = combine_ != CombineOp::kNone ? 0.27 * (double)b : 0.0;
-      return std::max<int64_t>(0, (int64_t)(2.25 * (double)b + 1.4 * (double)b + comb) - have);
+      // (a numeric kind's normalized keys: 8 B per record more, 0.125 of the bytes at 64 B records)
+      const double norm = key_kind_numeric(kind_) ? 0.125 * (double)b : 0.0;
+      return std::max<int64_t>(0, (int64_t)(2.25 * (double)b + 1.4 * (double)b + comb + norm) - have);
     });
   }
   if (total > round_bytes) {

@@ -175,9 +175,11 @@ class StagedMerge {
   CombineOp hybrid_combine_ = CombineOp::kNone, lpq_combine_ = CombineOp::kNone;
   // The budget counts ~3x the input per merge; a combining merge holds 17 B per record more (group index,
   // sums: 0.27 of the input at 64 B records, as the device path's admission counts them), so its input
-  // shrinks by 3 / 3.27: an RPQ round's target of half the budget, and an LPQ group's whole budget.
-  static int64_t less_combine(int64_t b, CombineOp op) {
-    return op != CombineOp::kNone ? (int64_t)((double)b * (3.0 / 3.27)) : b;
+  // shrinks by 3 / 3.27: an RPQ round's target of half the budget, and an LPQ group's whole budget. A numeric
+  // key kind (mapred.uda.key.order=hadoop) holds its normalized keys, 8 B per record (0.125 of the input), as well.
+  int64_t less_combine(int64_t b, CombineOp op) const {
+    const double extra = (op != CombineOp::kNone ? 0.27 : 0.0) + (key_kind_numeric(t_.kind_) ? 0.125 : 0.0);
+    return extra > 0 ? (int64_t)((double)b * (3.0 / (3.0 + extra))) : b;
   }
   int64_t round_target() const { return less_combine(budget_ / 2, hybrid_combine_); }
   // (with direct RPQ there is no LPQ merge: the budget only decides when the task stops being an online one)

@@ -76,6 +76,17 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
     res.checksum_ms += ws.checksum.ms();
     ws.checksum.reset();
   };
+  // a numeric kind's key of the wrong length (gpu::BadKeyError): the failure names the map output
+  auto merge_runs = [&](const std::vector<const uint8_t*>& runs, const std::vector<int64_t>& lens, uint8_t* out,
+                        int64_t total, const gpu::GenericMerger::RoundFn& fn) {
+    try {
+      return ws.merger.merge(runs, lens, (int)kind, out, total, spacing, s, fn, round_bytes, combine);
+    } catch (const gpu::BadKeyError& e) {
+      std::string who = e.run >= 0 && (size_t)e.run < in_runs.size() ? name_of(in_runs[(size_t)e.run]) : std::string("?");
+      if (who == "?") who = "#" + std::to_string(e.run);
+      throw UdaError(key_bad_length_message(kind, e.klen, "map output " + who));
+    }
+  };
   gpu::GenericMerger::RoundFn timed;
   if (on_round)
     timed = [&](const std::vector<int64_t>& cuts, int64_t records, bool last) {
@@ -115,8 +126,7 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
     }
     auto t1 = std::chrono::steady_clock::now();
     ws.h2d_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
-    gpu::GenericMergeResult r =
-        ws.merger.merge(runs, lens, (int)kind, ws.out.as<uint8_t>(), total, spacing, s, timed, round_bytes, combine);
+    gpu::GenericMergeResult r = merge_runs(runs, lens, ws.out.as<uint8_t>(), total, timed);
     HIP_CHECK(hipStreamSynchronize(s));
     ws.device_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count() - round_ms;
     res.bytes = r.bytes;
@@ -234,8 +244,7 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
     res.decoded_blocks = (int64_t)plan.descs.size();
   }
   host_raw.clear();
-  gpu::GenericMergeResult r =
-      ws.merger.merge(runs, bytes, (int)kind, out.as<uint8_t>(), total, spacing, s, timed, round_bytes, combine);
+  gpu::GenericMergeResult r = merge_runs(runs, bytes, out.as<uint8_t>(), total, timed);
   HIP_CHECK(hipStreamSynchronize(s));
   ws.device_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count() - round_ms;
   if (tm) trace::host_event("dm_merge", total, (int64_t)ptrs.size(), tm, trace::now_ns());

@@ -463,7 +463,11 @@ void ReduceTask::on_init(const InitParams& p_in) {
     p.local_dirs = canon;
   }
   init_ = p;
-  kind_ = key_kind_from_class(p.key_class.c_str());
+  // reference (default): the reference's three comparators; hadoop: Hadoop's own order for the numeric classes
+  const std::string ko = host_->get_conf("mapred.uda.key.order", "reference");
+  if (!key_order_from_conf(ko, &key_order_))
+    throw ProtocolError("unknown mapred.uda.key.order \"" + ko + "\" (reference or hadoop)");
+  kind_ = key_kind_from_class(p.key_class.c_str(), key_order_);
   if (kind_ == KeyKind::kUnsupported)
     throw ProtocolError("using compare function for unsupported type: " + p.key_class);
   bool unsup = false;
@@ -573,6 +577,7 @@ void ReduceTask::on_init(const InitParams& p_in) {
     std::lock_guard<std::mutex> g(st_mu_);
     st_.backend = backend_;
     st_.combine = combine_op_name(combine_);
+    st_.key_order = key_order_name(key_order_);
     st_.fetch_buf_bytes = fetch_buf_;
     st_.uncomp_buf_bytes = uncomp_buf;
   }
@@ -657,7 +662,9 @@ std::string ReduceTask::checkpoint_path() const {
       key.find_first_not_of("0123456789", u + 1) == std::string::npos)
     key.resize(u);
   const std::string dir = init_.local_dirs.empty() ? std::string("/tmp") : init_.local_dirs[0];
-  return dir + "/uda." + key + ".lpq.manifest";
+  // LPQ files are sorted in the key order of the attempt that wrote them: an attempt under another order
+  // finds no manifest under its own name and starts over
+  return dir + "/uda." + key + (key_order_ == KeyOrder::kHadoop ? ".hadoop" : "") + ".lpq.manifest";
 }
 
 // Manifest lines: "lpq <index> <bytes> <path> <map_id,map_id,...>". An entry is taken only if it
@@ -804,6 +811,7 @@ std::unique_ptr<Segment> ReduceTask::segment_for(std::shared_ptr<MofFetcher> f, 
   auto seg = std::make_unique<StreamSegment>(
       [f](uint8_t* dst, int64_t cap) { return f->pull(dst, cap); }, buffer_size_);
   seg->index = index;
+  seg->name = f->params().map_id;
   return seg;
 }
 
@@ -1100,7 +1108,7 @@ std::string ReduceTask::stats_json() const {
     << ",\"restored_maps\":" << s.restored_maps << ",\"device_descriptors\":" << s.device_descriptors << ",\"unmapped_descriptors\":" << s.unmapped_descriptors << ",\"unmapped_reason\":\"" << json_escape(s.unmapped_reason) << "\"" << ",\"descriptor_map_ms\":" << s.descriptor_map_ms << ",\"fetch_cmd_wait_ms\":" << s.fetch_cmd_wait_ms << ",\"fetch_ack_wait_ms\":" << s.fetch_ack_wait_ms << ",\"merge_start_boot_ms\":" << std::fixed << std::setprecision(1) << s.merge_start_boot_ms << ",\"fetch_sent_boot_ms\":" << s.fetch_sent_boot_ms << std::defaultfloat << std::setprecision(6) << ",\"first_data_ms\":" << s.first_data_ms << ",\"gpu_ws_bytes\":" << s.gpu_ws_bytes
     << ",\"host_fetched_bytes\":" << s.host_fetched_bytes << ",\"local_read_bytes\":" << s.local_read_bytes << ",\"hbm_wait_ms\":" << s.hbm_wait_ms
     << ",\"hbm_reserved\":" << s.hbm_reserved << ",\"round_bytes\":" << s.round_bytes << ",\"gpu_device\":" << s.gpu_device << ",\"merge_path\":\"" << s.merge_path << "\""
-    << ",\"combine\":\"" << s.combine << "\",\"combine_in_records\":" << s.combine_in_records
+    << ",\"key_order\":\"" << s.key_order << "\",\"combine\":\"" << s.combine << "\",\"combine_in_records\":" << s.combine_in_records
     << ",\"combine_groups\":" << s.combine_groups << ",\"merge_rounds\":" << s.merge_rounds
     << ",\"ifile_checksum\":\"" << s.ifile_checksum << "\",\"checksum_partitions\":" << s.checksum_partitions
     << ",\"checksum_bytes\":" << s.checksum_bytes << ",\"gpu_checksum_ms\":" << s.gpu_checksum_ms

@@ -96,6 +96,7 @@ struct ReduceStats {
   // delivered the uncombined stream; merged records that went into the combiner and the groups (records)
   // it delivered. records / bytes_delivered / buffers count what was delivered.
   std::string combine = "none";
+  std::string key_order = "reference";  // mapred.uda.key.order
   int64_t combine_in_records = 0, combine_groups = 0;
   int64_t merge_rounds = 0;     // GPU: hand-overs of device merges' output (rounds of mapred.uda.gpu.merge.round.bytes)
   // mapred.uda.ifile.checksum (uda/ifile.h): "none" (no partition carried a trailer), "verified", "off"
@@ -238,6 +239,7 @@ class ReduceTask {
   Host* host_;
   InitParams init_;
   KeyKind kind_ = KeyKind::kText;
+  KeyOrder key_order_ = KeyOrder::kReference;  // mapred.uda.key.order
   Codec codec_ = Codec::kNone;
   int64_t buffer_size_ = 0;        // per fetch buffer (pair = 2 of these)
   int64_t direct_chunk_ = 0;       // request size of fetch_direct (mapred.uda.fetch.request.bytes, >= buffer_size_)

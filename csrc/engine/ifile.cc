@@ -140,6 +140,13 @@ bool MergeQueue::less(const Segment* a, const Segment* b) {
 
 void MergeQueue::normalize(Segment* s) {
   const RecordView& r = s->cur();
+  if (key_kind_numeric(kind_)) {  // every record of the merge passes here once: where a bad key length is found
+    bool ok;
+    s->norm = KeyNorm{key_sortable(kind_, r.key, r.klen, &ok), 0, 8, 0};
+    if (!ok)
+      throw UdaError(key_bad_length_message(kind_, r.klen, "map output " + (s->name.empty() ? "#" + std::to_string(s->index) : s->name)));
+    return;
+  }
   s->norm = key_normalize(kind_, r.key, r.klen);
 }
 

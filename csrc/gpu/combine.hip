@@ -62,7 +62,15 @@ __device__ __forceinline__ bool same_key(const GenericKeyCtx& ctx, const Elem& a
 
 // Value bytes of record g from the side tables: record size less the headers, the key's class prefix
 // (both lie between recptr and keyptr) and the key content.
+// Numeric kinds: keyptr points at the normalized key, outside the record, so the value length is read from
+// the record's second header (ctx.normkey is a kernel argument: the branch is uniform).
 __device__ __forceinline__ int64_t value_bytes(const GenericKeyCtx& ctx, uint64_t g) {
+  if (ctx.normkey) {
+    const uint8_t* rec = ctx.recptr[g];
+    int64_t vl = 0;
+    vint_decode(rec + vint_decode_size((int8_t)rec[0]), 9, &vl);
+    return vl;
+  }
   return (int64_t)ctx.reclen[g] - (int64_t)(ctx.keyptr[g] - ctx.recptr[g]) - (int64_t)ctx.keylen[g];
 }
 

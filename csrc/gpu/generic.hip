@@ -11,6 +11,7 @@
 // in merged order gives every record its output offset; a wave copies 64 records at a time with
 // all lanes on each record (byte-granular, records are not aligned).
 #include <cstdlib>
+#include <stdexcept>
 #include "generic_cmp.h"
 #include "kernels.h"
 #include "uda/compare.h"
@@ -258,6 +259,14 @@ __device__ __forceinline__ void f1_step(BP buf, int lim, int64_t nrel64, int nre
     fallback = fallback || !(b0 >= 1 && rd(p + 2) == b0 - 1);
   else if (key_kind == (int)KeyKind::kBytes && (b0 | b1) >= 0 && p + 6 <= lim)
     fallback = fallback || !(b0 >= 4 && rd(p + 2) == 0 && rd(p + 3) == 0 && rd(p + 4) == 0 && (rd(p + 5) & 0xFF) == b0 - 4);
+  else if (key_kind >= (int)KeyKind::kByte && (b0 | b1) >= 0) {
+    // numeric kinds: the fixed key length of the class, or a VInt / VLong as long as its first byte says
+    const int w = key_fixed_bytes((KeyKind)key_kind);
+    if (w != 0)
+      fallback = fallback || b0 != w;
+    else if (p + 3 <= lim)
+      fallback = fallback || !(b0 >= 1 && vint_decode_size(rd(p + 2)) == b0);
+  }
   const bool bad = sz <= 0;
   const int np = p + sz;
   const bool fin = !bad && (np >= end_rel || fallback);
@@ -593,6 +602,37 @@ __global__ void __launch_bounds__(256) normalize_kernel(GenericKeyCtx ctx, const
   ctx.reclen[g] = (int32_t)(ctx.offsets[r][pos + 1] - ctx.offsets[r][pos]);
 }
 
+// F2 of the numeric kinds: the key's sortable word is the whole content. It goes into Elem.hi and, big-endian,
+// into the record's 8 bytes of ctx.normkey, where keyptr then points: F3, the combiner and the streamed rounds
+// read normalized bytes through the same side tables. A key of the wrong length is reported through
+// *ctx.badkey (its keylen entry keeps the length found, for the message); nothing is delivered then.
+__global__ void __launch_bounds__(256) normalize_numeric_kernel(GenericKeyCtx ctx, const int64_t* elem_off, int nruns,
+                                                                int64_t total, Elem* out) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= total) return;
+  const int r = find_run(elem_off, nruns, g);
+  const int64_t pos = g - elem_off[r];
+  const uint8_t* rec = ctx.bases[r] + ctx.offsets[r][pos];
+  int64_t kl = 0, vl = 0;
+  const int a = vint_decode(rec, 9, &kl);
+  const int b = vint_decode(rec + a, 9, &vl);
+  const uint8_t* key = rec + a + b;
+  bool ok;
+  // (a key longer than 9 bytes fits no numeric kind: key_sortable reads nothing of it)
+  const uint64_t sw = key_sortable((KeyKind)ctx.kind, key, (int)(kl > 16 ? 16 : kl), &ok);
+  if (!ok) atomicMin(ctx.badkey, (unsigned long long)g);
+  Elem e;
+  e.hi = sw;
+  e.lo = (8ull << 48) | (uint64_t)g;
+  out[g] = e;
+  uint8_t* nk = ctx.normkey + 8 * g;
+  *reinterpret_cast<uint64_t*>(nk) = __builtin_bswap64(sw);  // normkey is 8-byte aligned
+  ctx.keyptr[g] = nk;
+  ctx.keylen[g] = ok ? 8 : (int32_t)(kl > INT32_MAX ? INT32_MAX : kl);
+  ctx.recptr[g] = rec;
+  ctx.reclen[g] = (int32_t)(ctx.offsets[r][pos + 1] - ctx.offsets[r][pos]);
+}
+
 __global__ void __launch_bounds__(256) record_sizes_kernel(GenericKeyCtx ctx, const Elem* elems, int64_t n,
                                                            int64_t* sizes) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -878,7 +918,14 @@ int64_t f1_chunk_bytes() { return kF1Chunk; }
 
 void launch_normalize_generic(GenericKeyCtx ctx, const int64_t* elem_off, int nruns, int64_t total, Elem* out,
                               hipStream_t s) {
+  if (ctx.badkey) (void)hipMemsetAsync(ctx.badkey, 0xFF, sizeof(unsigned long long), s);
   if (total <= 0) return;
+  if (key_kind_numeric((KeyKind)ctx.kind)) {
+    if (!ctx.normkey || !ctx.badkey) throw std::invalid_argument("launch_normalize_generic: a numeric kind needs normkey and badkey");
+    hipLaunchKernelGGL(normalize_numeric_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ctx, elem_off,
+                       nruns, total, out);
+    return;
+  }
   hipLaunchKernelGGL(normalize_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, ctx, elem_off,
                      nruns, total, out);
 }

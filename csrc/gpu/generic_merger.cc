@@ -1,9 +1,11 @@
 #include "generic_merger.h"
 #include "merge_plan.h"
 
+#include "uda/compare.h"
 #include "uda/error.h"
 #include "uda/log.h"
 #include "uda/trace.h"
+#include "uda/vint.h"
 
 #include <algorithm>
 #include <chrono>
@@ -68,7 +70,7 @@ void GenericMerger::reserve_combine(int64_t records) {
 int64_t GenericMerger::workspace_bytes() const {
   int64_t b = 0;
   for (const DeviceBuffer* x : {&eoff_, &rounds_, &elems_a_, &elems_b_, &splits_, &sizes_, &out_off_, &scan_tmp_, &cuts_,
-                                &offsets_, &tables_, &side_, &ck_, &f1ws_, &gidx_, &sums_, &cflag_})
+                                &offsets_, &tables_, &side_, &ck_, &f1ws_, &gidx_, &sums_, &cflag_, &normkey_})
     b += (int64_t)x->size();
   for (const auto& k : gk_)
     for (const DeviceBuffer* x : {&k.tab, &k.samp, &k.sa, &k.sb, &k.bounds, &k.split, &k.hist, &k.flag}) b += (int64_t)x->size();
@@ -311,10 +313,29 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
     res.cuts = {0};
     return res;
   }
+  const bool numeric = key_kind_numeric((KeyKind)kind);
+  if (numeric) {  // the side buffer of normalized keys (8 B per record) and the bad-key ordinal
+    if (normkey_.size() < (size_t)total * 8) normkey_.alloc_local((size_t)total * 8 + (size_t)total + 64);
+    if (cflag_.size() < 64) cflag_.alloc_local(64);
+    ctx.normkey = normkey_.as<uint8_t>();
+    ctx.badkey = reinterpret_cast<unsigned long long*>(cflag_.as<uint8_t>() + 16);
+  }
   // ---- F2: normalize
   Elem* cur = elems_a_.as<Elem>();
   Elem* nxt = elems_b_.as<Elem>();
   launch_normalize_generic(ctx, d_eoff, K, total, cur, s);
+  if (numeric) {
+    // a key of the wrong length fails the merge here, before F3 and before anything is handed over
+    unsigned long long bad = 0;
+    HIP_CHECK(hipMemcpyAsync(&bad, ctx.badkey, 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (bad != ~0ull) {
+      int32_t kl = 0;
+      HIP_CHECK(hipMemcpy(&kl, ctx.keylen + bad, 4, hipMemcpyDeviceToHost));
+      const int run = (int)(std::upper_bound(eoff.begin(), eoff.end(), (int64_t)bad) - eoff.begin()) - 1;
+      throw BadKeyError(key_bad_length_message((KeyKind)kind, kl, "run " + std::to_string(run) + " of the merge"), run, kl);
+    }
+  }
   phase("f2_normalize");
   // ---- F3: single-pass K-way merge (generic_kway.hip) when K allows, else the pairwise tree;
   // per-pass descriptors are small host tables uploaded per pass
@@ -597,7 +618,16 @@ GenericMergeResult GenericMerger::merge(const std::vector<const uint8_t*>& runs,
         HIP_CHECK(hipMemcpy(&kp, ctx.keyptr + g, 8, hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(&rl, ctx.reclen + g, 4, hipMemcpyDeviceToHost));
         HIP_CHECK(hipMemcpy(&kl, ctx.keylen + g, 4, hipMemcpyDeviceToHost));
-        const int64_t vlen = (int64_t)rl - (kp - rp) - kl;
+        int64_t vlen = (int64_t)rl - (kp - rp) - kl;
+        if (numeric) {  // keyptr is the normalized key: the raw key and the value length from the record's headers
+          uint8_t hdr[18] = {0};
+          HIP_CHECK(hipMemcpy(hdr, rp, (size_t)std::min<int32_t>(rl, 18), hipMemcpyDeviceToHost));
+          int64_t rkl = 0;
+          const int ha = vint_decode(hdr, 9, &rkl);
+          const int hb = vint_decode(hdr + ha, 9, &vlen);
+          kp = rp + ha + hb;
+          kl = (int32_t)rkl;
+        }
         std::vector<uint8_t> key((size_t)std::min<int32_t>(kl, 64));
         if (!key.empty()) HIP_CHECK(hipMemcpy(key.data(), kp, key.size(), hipMemcpyDeviceToHost));
         throw UdaError(combine_bad_value_message(combine, key.data(), (int64_t)key.size(), vlen));

@@ -10,6 +10,7 @@
 #include "device_engine.h"
 #include "kernels.h"
 #include "uda/combine.h"
+#include "uda/error.h"
 
 namespace uda {
 namespace gpu {
@@ -23,6 +24,14 @@ struct GenericMergeResult {
   int rounds = 0;             // on_round calls made
   int64_t held_records = 0;   // streamed under combine: sum over rounds of the elements of the open last group
                               // a round carried into the next one instead of delivering them
+};
+
+// A numeric kind (uda::key_kind_numeric) met a key of the wrong length: nothing was delivered. `run` is the
+// index of the run that holds the first such record, for callers that know the runs' names.
+struct BadKeyError : UdaError {
+  BadKeyError(const std::string& what, int run_, int64_t klen_) : UdaError(what), run(run_), klen(klen_) {}
+  int run;
+  int64_t klen;
 };
 
 class GenericMerger {
@@ -67,6 +76,7 @@ class GenericMerger {
   // combine workspace: group index (8 B) and sums (8 B) per record, the bad-value flag
   void reserve_combine(int64_t records);
   DeviceBuffer gidx_, sums_, cflag_;
+  DeviceBuffer normkey_;  // numeric kinds: the sortable word of every record, 8 bytes big-endian
   DeviceBuffer eoff_, rounds_, passtab_;  // passtab_: pairwise-tree pass tables (no hipMalloc/hipFree per merge)
   PinnedBuffer cuts_host_;
   std::vector<hipEvent_t> round_ev_;

@@ -19,12 +19,24 @@ namespace {
 constexpr int kSampleKey = 64;      // content bytes kept per sampled key (a bound may be any byte string)
 constexpr int kSamplesPerRound = 512;
 
-// Key content of the record at p (n bytes of stream left): pointer and length.
-__device__ __forceinline__ const uint8_t* rec_key(const uint8_t* p, int64_t n, int kind, int* len, int64_t* size) {
+// Key content of the record at p (n bytes of stream left): pointer and length. Numeric kinds: the content
+// is the key's sortable word, big-endian in the caller's `norm` (the bytes F2 will compare; a key of the
+// wrong length is the word 0 here and fails the task in F2 of its round).
+__device__ __forceinline__ const uint8_t* rec_key(const uint8_t* p, int64_t n, int kind, int* len, int64_t* size,
+                                                  uint8_t* norm) {
   int64_t kl = 0, vl = 0;
   const int a = vint_decode(p, (size_t)(n < 9 ? n : 9), &kl);
   const int b = vint_decode(p + a, (size_t)(n - a < 9 ? n - a : 9), &vl);
   const uint8_t* key = p + a + b;
+  if (key_kind_numeric((KeyKind)kind)) {
+    bool ok;
+    const int64_t left = n - a - b;  // key bytes inside the stream
+    const uint64_t sw = key_sortable((KeyKind)kind, key, (int)(kl > left ? 0 : kl > 16 ? 16 : kl), &ok);
+    for (int i = 0; i < 8; ++i) norm[i] = (uint8_t)(sw >> (56 - 8 * i));
+    *len = 8;
+    *size = a + b + kl + vl;
+    return norm;
+  }
   const int o = key_content_offset((KeyKind)kind, key, (int)kl);
   *len = (int)kl - o;
   *size = a + b + kl + vl;
@@ -60,7 +72,8 @@ __global__ void __launch_bounds__(256) gr_sample_kernel(uint8_t* const* bases, c
   if (pos >= rec_bytes[r]) return;  // the EOF marker
   int len = 0;
   int64_t size = 0;
-  const uint8_t* k = rec_key(bases[r] + pos, rec_bytes[r] - pos, kind, &len, &size);
+  uint8_t norm[8];
+  const uint8_t* k = rec_key(bases[r] + pos, rec_bytes[r] - pos, kind, &len, &size, norm);
   const int n = len < kSampleKey ? len : kSampleKey;
   for (int j = 0; j < n; ++j) keys[(int64_t)i * kSampleKey + j] = k[j];
   klen[i] = n;
@@ -88,7 +101,8 @@ __global__ void __launch_bounds__(64) gr_split_kernel(uint8_t* const* bases, con
     if (pos >= rb) return true;
     int len = 0;
     int64_t size = 0;
-    const uint8_t* k = rec_key(p + pos, rb - pos, kind, &len, &size);
+    uint8_t norm[8];
+    const uint8_t* k = rec_key(p + pos, rb - pos, kind, &len, &size, norm);
     return cmp_bound(k, len, bnd, bl) >= 0;
   };
   int64_t a = lo, b = hi;  // smallest c in [lo, hi] with not_below(c) (not_below(hi) is true)
@@ -112,7 +126,8 @@ __global__ void __launch_bounds__(64) gr_split_kernel(uint8_t* const* bases, con
     while (pos < end) {
       int len = 0;
       int64_t size = 0;
-      const uint8_t* k = rec_key(p + pos, rb - pos, kind, &len, &size);
+      uint8_t norm[8];
+      const uint8_t* k = rec_key(p + pos, rb - pos, kind, &len, &size, norm);
       if (cmp_bound(k, len, bnd, bl) >= 0) break;
       pos += size;
     }
@@ -138,17 +153,18 @@ __global__ void __launch_bounds__(64) gr_lastkey_kernel(uint8_t* const* bases, c
   if (c < lo) return;
   const uint8_t* p = bases[r];
   int64_t pos = ck_start[c], last = pos;
+  uint8_t norm[8];
   while (pos < rb) {
     int len = 0;
     int64_t size = 0;
-    (void)rec_key(p + pos, rb - pos, kind, &len, &size);
+    (void)rec_key(p + pos, rb - pos, kind, &len, &size, norm);
     if (size <= 0) break;
     last = pos;
     pos += size;
   }
   int len = 0;
   int64_t size = 0;
-  const uint8_t* k = rec_key(p + last, rb - last, kind, &len, &size);
+  const uint8_t* k = rec_key(p + last, rb - last, kind, &len, &size, norm);
   const int n = len < kSampleKey ? len : kSampleKey;
   for (int j = 0; j < n; ++j) keys[(int64_t)r * kSampleKey + j] = k[j];
   klen[r] = n;

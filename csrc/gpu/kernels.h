@@ -110,6 +110,9 @@ void launch_merge_pass(const Elem* in, Elem* out, PassDesc pd, const int64_t* sp
 // After F2 every record g (global ordinal, run-major) also has direct side tables so the merge and
 // the gather never re-parse headers: key content pointer/length and record pointer/length.
 // GENERIC Elem: hi = first 8 content bytes (big-endian), lo = min(content_len, 0xFFFF) << 48 | g.
+// Numeric kinds (uda::key_kind_numeric): the content of record g is its sortable word, written big-endian
+// at normkey + 8 g; keyptr[g] points there and keylen[g] = 8, so everything after F2 compares those bytes.
+// *badkey = lowest g whose key has the wrong length for the kind (~0: none).
 struct GenericKeyCtx {
   uint8_t* const* bases;
   const int64_t* const* offsets;
@@ -118,6 +121,8 @@ struct GenericKeyCtx {
   int32_t* keylen;          // [g] content length
   const uint8_t** recptr;   // [g] record start
   int32_t* reclen;          // [g] record size
+  uint8_t* normkey = nullptr;             // numeric kinds: [g] 8 bytes, else null
+  unsigned long long* badkey = nullptr;   // numeric kinds
 };
 void launch_merge_partition_generic(const Elem* in, PassDesc pd, int64_t* splits, GenericKeyCtx ctx,
                                     hipStream_t s);

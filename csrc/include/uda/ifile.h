@@ -49,6 +49,7 @@ class Segment {
   const RecordView& cur() const { return cur_; }
   int index = 0;          // stable tie-break (fetch order / map order)
   int64_t records = 0;    // records produced so far
+  std::string name;       // what the records come from (a map attempt id), for messages; may be empty
   KeyNorm norm{};         // normalized current key (first 16 content bytes), kept by MergeQueue
  protected:
   RecordView cur_;

@@ -231,10 +231,20 @@ CombineOp combine_op_arg(const std::string& v) {
   return op;
 }
 
-py::bytes cpu_merge_impl(const std::vector<std::string>& runs, const std::string& key_class, int64_t buf,
-                         std::vector<int64_t>* lens, CombineOp combine = CombineOp::kNone) {
-  KeyKind kind = key_kind_from_class(key_class.c_str());
+// The comparator kind of a key class under a mapred.uda.key.order value ("reference" or "hadoop").
+KeyKind key_kind_arg(const std::string& key_class, const std::string& key_order = "reference") {
+  KeyOrder order;
+  if (!key_order_from_conf(key_order, &order))
+    throw py::value_error("unknown key_order \"" + key_order + "\" (reference or hadoop)");
+  const KeyKind kind = key_kind_from_class(key_class.c_str(), order);
   if (kind == KeyKind::kUnsupported) throw py::value_error("unsupported key class");
+  return kind;
+}
+
+py::bytes cpu_merge_impl(const std::vector<std::string>& runs, const std::string& key_class, int64_t buf,
+                         std::vector<int64_t>* lens, CombineOp combine = CombineOp::kNone,
+                         const std::string& key_order = "reference") {
+  KeyKind kind = key_kind_arg(key_class, key_order);
   MergeQueue q(kind);
   for (size_t i = 0; i < runs.size(); ++i) {
     auto seg = std::make_unique<MemorySegment>(reinterpret_cast<const uint8_t*>(runs[i].data()), runs[i].size());
@@ -294,6 +304,21 @@ PYBIND11_MODULE(_uda_native, m) {
     return d;
   });
   m.def("key_kind", [](const std::string& cls) { return (int)key_kind_from_class(cls.c_str()); });
+  // key_kind under a mapred.uda.key.order value; -1 for a class that order does not support
+  m.def("key_kind_ordered", [](const std::string& cls, const std::string& key_order) {
+    KeyOrder order;
+    if (!key_order_from_conf(key_order, &order))
+      throw py::value_error("unknown key_order \"" + key_order + "\" (reference or hadoop)");
+    return (int)key_kind_from_class(cls.c_str(), order);
+  }, py::arg("cls"), py::arg("key_order"));
+  // the sortable word of a numeric key (uda/compare.h); ValueError for a key of the wrong length
+  m.def("key_sortable", [](int kind, py::bytes key) {
+    std::string k = key;
+    bool ok = false;
+    const uint64_t v = key_sortable((KeyKind)kind, reinterpret_cast<const uint8_t*>(k.data()), (int)k.size(), &ok);
+    if (!ok) throw py::value_error(key_bad_length_message((KeyKind)kind, (int64_t)k.size(), "key_sortable"));
+    return v;
+  });
   m.def("key_compare", [](int kind, py::bytes a, py::bytes b) {
     std::string sa = a, sb = b;
     return key_compare((KeyKind)kind, reinterpret_cast<const uint8_t*>(sa.data()), (int)sa.size(),
@@ -845,29 +870,28 @@ PYBIND11_MODULE(_uda_native, m) {
 
   // ---------------------------------------------------------------- CPU engine
   m.def("cpu_merge", [](const std::vector<std::string>& runs, const std::string& key_class, int64_t buf,
-                        const std::string& combine) {
+                        const std::string& combine, const std::string& key_order) {
     std::vector<int64_t> lens;
-    py::bytes out = cpu_merge_impl(runs, key_class, buf, &lens, combine_op_arg(combine));
+    py::bytes out = cpu_merge_impl(runs, key_class, buf, &lens, combine_op_arg(combine), key_order);
     return py::make_tuple(out, lens);
-  }, py::arg("runs"), py::arg("key_class"), py::arg("buf"), py::arg("combine") = "none");
+  }, py::arg("runs"), py::arg("key_class"), py::arg("buf"), py::arg("combine") = "none",
+        py::arg("key_order") = "reference");
   // Host reference of the reduce-side combiner (uda/combine.h) over a stream already in merged order.
-  m.def("combine_stream", [](const std::string& stream, const std::string& key_class, const std::string& op) {
-    KeyKind kind = key_kind_from_class(key_class.c_str());
-    if (kind == KeyKind::kUnsupported) throw py::value_error("unsupported key class");
+  m.def("combine_stream", [](const std::string& stream, const std::string& key_class, const std::string& op,
+                             const std::string& key_order) {
+    KeyKind kind = key_kind_arg(key_class, key_order);
     const std::vector<uint8_t> out =
         combine_stream(reinterpret_cast<const uint8_t*>(stream.data()), stream.size(), kind, combine_op_arg(op));
     return py::bytes(reinterpret_cast<const char*>(out.data()), out.size());
-  }, py::arg("stream"), py::arg("key_class"), py::arg("op"));
+  }, py::arg("stream"), py::arg("key_class"), py::arg("op"), py::arg("key_order") = "reference");
   // merged elements per workgroup of the device combiner's segmented sum (tests build groups around it)
   m.def("combine_tile", [] { return (int)gpu::kCombineTile; });
 
   // teravalidate: framing + order + checksum of a delivered stream, fed buffer by buffer
   py::class_<StreamValidator, std::shared_ptr<StreamValidator>>(m, "StreamValidator")
-      .def(py::init([](const std::string& key_class) {
-        KeyKind kind = key_kind_from_class(key_class.c_str());
-        if (kind == KeyKind::kUnsupported) throw py::value_error("unsupported key class");
-        return std::make_shared<StreamValidator>(kind);
-      }))
+      .def(py::init([](const std::string& key_class, const std::string& key_order) {
+        return std::make_shared<StreamValidator>(key_kind_arg(key_class, key_order));
+      }), py::arg("key_class"), py::arg("key_order") = "reference")
       .def("feed", [](StreamValidator& v, py::buffer b) {
         py::buffer_info bi = b.request();
         v.feed(static_cast<const uint8_t*>(bi.ptr), (size_t)(bi.size * bi.itemsize));
@@ -1668,9 +1692,8 @@ PYBIND11_MODULE(_uda_native, m) {
   // combine: "none" or an op of uda/combine.h (sum.int, sum.long, min.int, max.int, min.long, max.long,
   // sum.vint, sum.vlong): records then counts the groups delivered.
   m.def("gpu_merge_runs", [](const py::list& runs, const std::string& key_class, int64_t kv_buf, int device,
-                             const std::string& combine) {
-    KeyKind kind = key_kind_from_class(key_class.c_str());
-    if (kind == KeyKind::kUnsupported) throw py::value_error("unsupported key class");
+                             const std::string& combine, const std::string& key_order) {
+    KeyKind kind = key_kind_arg(key_class, key_order);
     const CombineOp cop = combine_op_arg(combine);
     std::vector<py::buffer_info> views;
     std::vector<const uint8_t*> host;
@@ -1743,7 +1766,7 @@ PYBIND11_MODULE(_uda_native, m) {
     }
     return py::make_tuple(out, cuts, records, passes, merge_ms, serial_runs, records_in);
   }, py::arg("runs"), py::arg("key_class"), py::arg("kv_buf") = 1 << 20, py::arg("device") = 0,
-        py::arg("combine") = "none");
+        py::arg("combine") = "none", py::arg("key_order") = "reference");
   // The same merge handed over in key-range rounds of about round_bytes (GenericMerger::merge's on_round,
   // recorded here). Returns (merged bytes, cuts, records, records merged, rounds, held records), rounds a
   // list of (records, absolute cuts) per on_round call. gpu_merge_streamed_last_rounds(): the on_round
@@ -1751,9 +1774,9 @@ PYBIND11_MODULE(_uda_native, m) {
   static std::atomic<int> streamed_last_rounds{0};
   m.def("gpu_merge_streamed_last_rounds", [] { return streamed_last_rounds.load(); });
   m.def("gpu_merge_runs_streamed", [](const py::list& runs, const std::string& key_class, int64_t kv_buf,
-                                      int64_t round_bytes, int device, const std::string& combine) {
-    KeyKind kind = key_kind_from_class(key_class.c_str());
-    if (kind == KeyKind::kUnsupported) throw py::value_error("unsupported key class");
+                                      int64_t round_bytes, int device, const std::string& combine,
+                                      const std::string& key_order) {
+    KeyKind kind = key_kind_arg(key_class, key_order);
     if (round_bytes <= 0) throw py::value_error("round_bytes must be positive");
     const CombineOp cop = combine_op_arg(combine);
     std::vector<py::buffer_info> views;
@@ -1815,7 +1838,7 @@ PYBIND11_MODULE(_uda_native, m) {
     return py::make_tuple(py::bytes(reinterpret_cast<const char*>(merged.data()), merged.size()), res.cuts, res.records,
                           res.records_in, rounds, res.held_records);
   }, py::arg("runs"), py::arg("key_class"), py::arg("kv_buf"), py::arg("round_bytes"), py::arg("device") = 0,
-        py::arg("combine") = "none");
+        py::arg("combine") = "none", py::arg("key_order") = "reference");
   // F8: sort TeraSort records (104-byte IFile records, no EOF marker) by their 10-byte key on the
   // device; returns (sorted bytes, device ms of the sort).
   m.def("gpu_sort_fixed", [](py::buffer b, int device, bool staged) {

@@ -103,7 +103,9 @@ class UdaConsumer:
         self.num_maps = num_maps
         self.reader = J2CQueueReader(max_len=kv_buf_size) if keep_records else None
         # teravalidate in native code (framing, order, checksum) without keeping the records
-        self.validator = native().StreamValidator(key_class) if validate else None
+        # (under the job's own key order: mapred.uda.key.order)
+        self.validator = (native().StreamValidator(key_class, str((conf or {}).get("mapred.uda.key.order", "reference")))
+                          if validate else None)
         self.bytes = 0
         self.buffers = 0
         self.maps_reported = 0

@@ -15,8 +15,11 @@ last_stats: dict = {}  # timing of the most recent merge_runs call (device merge
 
 
 def merge_runs(runs: list[bytes], key_class: str, device: str = "gpu", kv_buf: int = 1 << 20,
-               gpu_index: int = 0, combine: str = "none"):
-    """combine: "none" or an op of mapred.uda.merge.combine: equal keys are folded into the first record of
+               gpu_index: int = 0, combine: str = "none", key_order: str = "reference"):
+    """key_order: a value of mapred.uda.key.order. "reference": the reference's three comparators (numeric
+    keys by memcmp). "hadoop": Byte/Short/Int/Long/VInt/VLong/Float/DoubleWritable keys in the order of their
+    Hadoop comparators (uda/compare.h: key_sortable); a key of the wrong length raises.
+    combine: "none" or an op of mapred.uda.merge.combine: equal keys are folded into the first record of
     their group, on the device (csrc/gpu/combine.hip) or by the host reference.
       sum.int, sum.long                      4 / 8-byte big-endian values, wrapping sum
       min.int, max.int, min.long, max.long   the same values, signed minimum / maximum
@@ -27,12 +30,12 @@ def merge_runs(runs: list[bytes], key_class: str, device: str = "gpu", kv_buf: i
         if n.device_count() <= 0:
             raise RuntimeError("merge_runs(device='gpu'): no HIP device visible")
         merged, cuts, _records, _passes, merge_ms, serial, records_in = n.gpu_merge_runs(
-            list(runs), key_class, kv_buf - 2, gpu_index, combine)
+            list(runs), key_class, kv_buf - 2, gpu_index, combine, key_order)
         last_stats.update(device="gpu", records=_records, passes=_passes, merge_ms=merge_ms, f1_serial_runs=serial,
                           records_in=records_in)
         return merged, cuts
     if device == "cpu":
-        out, lens = n.cpu_merge(list(runs), key_class, kv_buf, combine)
+        out, lens = n.cpu_merge(list(runs), key_class, kv_buf, combine, key_order)
         # cpu_merge already appended the EOF marker and packed greedily
         body = out[:-2]
         cuts, pos = [0], 0
@@ -45,7 +48,7 @@ def merge_runs(runs: list[bytes], key_class: str, device: str = "gpu", kv_buf: i
 
 
 def merge_runs_streamed(runs: list[bytes], key_class: str, kv_buf: int = 1 << 20, round_bytes: int = 256 << 20,
-                        gpu_index: int = 0, combine: str = "none"):
+                        gpu_index: int = 0, combine: str = "none", key_order: str = "reference"):
     """The device merge handed over in key-range rounds of about round_bytes of input, as a reduce task
     receives it. Returns (merged record bytes, cuts, stats): stats has records, records_in, held_records and
     rounds, a list of (records, cuts of that round) per hand-over. Under combine a round ends on a group
@@ -54,7 +57,7 @@ def merge_runs_streamed(runs: list[bytes], key_class: str, kv_buf: int = 1 << 20
     if n.device_count() <= 0:
         raise RuntimeError("merge_runs_streamed: no HIP device visible")
     merged, cuts, records, records_in, rounds, held = n.gpu_merge_runs_streamed(
-        list(runs), key_class, kv_buf - 2, round_bytes, gpu_index, combine)
+        list(runs), key_class, kv_buf - 2, round_bytes, gpu_index, combine, key_order)
     return merged, cuts, dict(records=records, records_in=records_in, rounds=rounds, held_records=held)
 
 
