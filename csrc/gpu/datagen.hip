@@ -8,6 +8,9 @@
 // the runs of one reducer interleave randomly (what a range-partitioned TeraSort produces).
 #include "kernels.h"
 
+#include <stdexcept>
+#include <string>
+
 namespace uda {
 namespace gpu {
 
@@ -196,6 +199,14 @@ void launch_sample_fixed(uint8_t* const* bases, const int64_t* nrec, int nruns, 
   if (total <= 0) return;
   hipLaunchKernelGGL(sample_fixed_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
                      bases, nrec, nruns, every, sample_off, total, out);
+}
+
+void require_teragen_spans(const int64_t* nrec, const uint64_t* key_span, int nruns) {
+  for (int r = 0; r < nruns; ++r)
+    if (nrec[r] > 0 && key_span[r] < (uint64_t)nrec[r])
+      throw std::invalid_argument("teragen: run " + std::to_string(r) + " has " + std::to_string(nrec[r]) +
+                                  " records in a key span of " + std::to_string(key_span[r]) +
+                                  " (a sorted run needs key_span >= nrec)");
 }
 
 void launch_teragen(uint8_t* const* bases, const int64_t* nrec, const uint64_t* key_lo,

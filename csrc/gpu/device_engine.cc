@@ -966,6 +966,9 @@ void ShuffleJob::generate() {
       seeds[r] = cfg_.seed ^ (0x9E3779B97F4A7C15ull * (gmap + 1)) ^ (0xC2B2AE3D27D4EB4Full * (d + 1));
       max_n = std::max(max_n, run_nrec_[r]);
     }
+  // sorted generation strides each run's keys over its span (kernels.h: key_span >= nrec); unsorted
+  // generation draws them and the map-side sort orders them
+  if (!cfg_.map_sort) require_teragen_spans(run_nrec_.data(), key_span.data(), nruns);
   DeviceBuffer d_b(nruns * sizeof(uint8_t*)), d_n(nruns * 8), d_lo(nruns * 8), d_sp(nruns * 8), d_sd(nruns * 8),
       d_ck(nruns * 8);
   HIP_CHECK(hipMemcpy(d_b.as(), gen_bases.data(), nruns * sizeof(uint8_t*), hipMemcpyHostToDevice));
@@ -2088,6 +2091,7 @@ StepStats ShuffleJob::run_step(bool validate) {
     }
   }
 
+  DeviceBuffer fault_scratch;  // MERGE_SWAP's third record; allocated when the fault fires
   for (int q = 0; q < Q_; ++q) {
     trace::Range tr_round("uda.round");
     const int slot = q % kSlots;
@@ -2179,6 +2183,34 @@ StepStats ShuffleJob::run_step(bool validate) {
     HIP_CHECK(hipGetLastError());
     st.merge_passes = std::max(st.merge_passes, merger_->last_passes());
     if (validate) {
+      // Fault sites (uda/fault.h), polled once per round: a wrong merge the checks below must report. Both
+      // act on the first reducer group with two or more records in this round's output slot.
+      const bool swap_fault = fault_hit("MERGE_SWAP"), flip_fault = fault_hit("MERGE_FLIP");
+      if (swap_fault || flip_fault) {
+        int64_t at = 0;
+        int gi = 0;
+        while (gi < R_ && rp.group_recs[gi] < 2) at += rp.group_recs[gi++];
+        if (gi < R_) {
+          uint8_t* r0 = out + at * kTeraRecordBytes;
+          uint8_t* r1 = r0 + kTeraRecordBytes;
+          if (swap_fault) {  // records 0 and 1 exchanged: one inverted pair, the same checksum
+            if (!fault_scratch.size()) fault_scratch.alloc_local(kTeraRecordBytes);
+            uint8_t* t = fault_scratch.as<uint8_t>();
+            HIP_CHECK(hipMemcpyAsync(t, r0, kTeraRecordBytes, hipMemcpyDeviceToDevice, s_compute_));
+            HIP_CHECK(hipMemcpyAsync(r0, r1, kTeraRecordBytes, hipMemcpyDeviceToDevice, s_compute_));
+            HIP_CHECK(hipMemcpyAsync(r1, t, kTeraRecordBytes, hipMemcpyDeviceToDevice, s_compute_));
+          }
+          if (flip_fault) {  // one value bit of record 0: the same order, another checksum
+            uint8_t b = 0;
+            uint8_t* p = r0 + kTeraKeyOffset + kTeraKeyBytes + 1 + 40;
+            HIP_CHECK(hipMemcpyAsync(&b, p, 1, hipMemcpyDeviceToHost, s_compute_));
+            HIP_CHECK(hipStreamSynchronize(s_compute_));
+            b ^= 0x01;
+            HIP_CHECK(hipMemcpyAsync(p, &b, 1, hipMemcpyHostToDevice, s_compute_));
+            HIP_CHECK(hipStreamSynchronize(s_compute_));
+          }
+        }
+      }
       int64_t goff = 0;
       for (int i = 0; i < R_; ++i) {
         const int64_t g = rp.group_recs[i];

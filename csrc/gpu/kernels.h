@@ -52,6 +52,12 @@ struct RunDesc {
 // order-independent checksum (sum of record_hash) per run into `run_checksum[r]` (zero it first).
 // unsorted != 0: keys uniform in the same range in generation order (a map task's input before its
 // sort; launch_sort_fixed_run turns each run into a sorted map-output partition).
+// Contract (sorted mode): key_span[r] >= nrec[r] for every run. Record i's key starts at
+// key_lo[r] + i * (key_span[r] / nrec[r]); with a span below the record count that stride is 0, every
+// record draws the same first 8 key bytes and random last two, and the "sorted" run is not sorted.
+// require_teragen_spans (host, no device needed) throws std::invalid_argument for such a plan; callers
+// check before they launch.
+void require_teragen_spans(const int64_t* nrec, const uint64_t* key_span, int nruns);
 void launch_teragen(uint8_t* const* bases, const int64_t* nrec, const uint64_t* key_lo,
                     const uint64_t* key_span, const uint64_t* seeds, int nruns, int64_t max_nrec,
                     unsigned long long* run_checksum, hipStream_t s, int unsorted = 0);

@@ -1880,6 +1880,214 @@ PYBIND11_MODULE(_uda_native, m) {
     }
     return py::make_tuple(out, (double)ms);
   }, py::arg("records"), py::arg("device") = 0, py::arg("staged") = false);
+
+  // Test hooks of the device validators and of the TeraGen kernel (tests/test_gpu_validate.py): each runs the
+  // launcher on a stream of its own, synchronises and returns what the device wrote.
+  struct TestStream {
+    hipStream_t s = nullptr;
+    TestStream() { HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+    ~TestStream() {
+      (void)hipStreamSynchronize(s);
+      (void)hipStreamDestroy(s);
+    }
+  };
+  // FIXED10 slices laid end to end in one device buffer (a record is 104 bytes, so every slice is 8-byte aligned)
+  struct DeviceSlices {
+    gpu::DeviceBuffer data, descs;
+    int64_t largest = 0;
+    DeviceSlices(const std::vector<std::string>& slices, hipStream_t s) {
+      size_t total = 0;
+      for (const auto& b : slices) {
+        if (b.size() % (size_t)gpu::kTeraRecordBytes) throw py::value_error("need whole 104-byte records");
+        total += b.size();
+      }
+      data.alloc(std::max<size_t>(total, 16));
+      std::vector<gpu::RunDesc> rd(slices.size());
+      size_t at = 0;
+      for (size_t i = 0; i < slices.size(); ++i) {
+        rd[i].base = data.as<uint8_t>() + at;
+        rd[i].nbytes = (int64_t)slices[i].size();
+        rd[i].nrec = rd[i].nbytes / gpu::kTeraRecordBytes;
+        rd[i].offsets = nullptr;
+        largest = std::max(largest, rd[i].nrec);
+        if (!slices[i].empty())
+          HIP_CHECK(hipMemcpyAsync(data.as<uint8_t>() + at, slices[i].data(), slices[i].size(), hipMemcpyHostToDevice, s));
+        at += slices[i].size();
+      }
+      descs.alloc(std::max<size_t>(rd.size() * sizeof(gpu::RunDesc), 16));
+      if (!rd.empty())
+        HIP_CHECK(hipMemcpyAsync(descs.as(), rd.data(), rd.size() * sizeof(gpu::RunDesc), hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipStreamSynchronize(s));  // rd goes out of scope
+    }
+  };
+  // Order errors, checksum and last key of the chunks taken as one stream: one launch_validate_fixed per
+  // non-empty chunk, chained as ShuffleJob::run_step chains a reducer's rounds.
+  m.def("gpu_validate_fixed", [](const std::vector<std::string>& chunks, int device) {
+    for (const auto& c : chunks)
+      if (c.size() % (size_t)gpu::kTeraRecordBytes) throw py::value_error("need whole 104-byte records");
+    unsigned long long host[8] = {0};  // stats[2], group_ck, pad, prev key, last key
+    bool any = false;
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      gpu::DeviceBuffer state(sizeof(host));
+      std::vector<gpu::DeviceBuffer> bufs;
+      TestStream ts;
+      unsigned long long* stats = state.as<unsigned long long>();
+      gpu::Elem* prev = reinterpret_cast<gpu::Elem*>(stats + 4);
+      gpu::Elem* last = prev + 1;
+      HIP_CHECK(hipMemsetAsync(state.as(), 0, sizeof(host), ts.s));
+      for (const auto& c : chunks) {
+        if (c.empty()) continue;
+        bufs.emplace_back(std::max<size_t>(c.size(), 16));
+        HIP_CHECK(hipMemcpyAsync(bufs.back().as(), c.data(), c.size(), hipMemcpyHostToDevice, ts.s));
+        gpu::launch_validate_fixed(bufs.back().as<uint8_t>(), (int64_t)c.size() / gpu::kTeraRecordBytes, prev,
+                                   any ? 1 : 0, last, stats, ts.s, stats + 2);
+        HIP_CHECK(hipMemcpyAsync(prev, last, sizeof(gpu::Elem), hipMemcpyDeviceToDevice, ts.s));
+        any = true;
+      }
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipMemcpyAsync(host, state.as(), sizeof(host), hipMemcpyDeviceToHost, ts.s));
+      HIP_CHECK(hipStreamSynchronize(ts.s));
+    }
+    char key[10];
+    for (int b = 0; b < 8; ++b) key[b] = (char)(host[6] >> (56 - 8 * b));
+    key[8] = (char)(host[7] >> 56);
+    key[9] = (char)(host[7] >> 48);
+    py::dict d;
+    d["order_errors"] = host[0];
+    d["checksum"] = host[1];
+    d["group_ck"] = host[2];
+    d["last_key"] = py::bytes(key, any ? sizeof(key) : 0);
+    return d;
+  }, py::arg("chunks"), py::arg("device") = 0);
+  // launch_slice_checksums over the slices; max_nrec (default: the largest slice) sizes the grid as the
+  // engine does, so 1 gives one block per slice. The output starts as ff bytes: the launcher zeroes it.
+  m.def("gpu_slice_checksums", [](const std::vector<std::string>& slices, const py::object& max_nrec, int device) {
+    const int64_t forced = max_nrec.is_none() ? -1 : max_nrec.cast<int64_t>();
+    const int n = (int)slices.size();
+    if (n > 65535) throw py::value_error("more slices than one launch takes (65535)");
+    std::vector<uint64_t> out((size_t)n);
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      TestStream ts;
+      DeviceSlices in(slices, ts.s);
+      gpu::DeviceBuffer ck(std::max<size_t>((size_t)n * 8, 16));
+      HIP_CHECK(hipMemsetAsync(ck.as(), 0xFF, ck.size(), ts.s));
+      gpu::launch_slice_checksums(in.descs.as<gpu::RunDesc>(), n, forced >= 0 ? forced : in.largest,
+                                  ck.as<unsigned long long>(), ts.s);
+      HIP_CHECK(hipGetLastError());
+      if (n) HIP_CHECK(hipMemcpyAsync(out.data(), ck.as(), (size_t)n * 8, hipMemcpyDeviceToHost, ts.s));
+      HIP_CHECK(hipStreamSynchronize(ts.s));
+    }
+    return out;
+  }, py::arg("slices"), py::arg("max_nrec") = py::none(), py::arg("device") = 0);
+  // launch_check_fixed over the slices: True when every record has the TeraSort layout.
+  m.def("gpu_check_fixed", [](const std::vector<std::string>& slices, const py::object& max_nrec, int device) {
+    const int64_t forced = max_nrec.is_none() ? -1 : max_nrec.cast<int64_t>();
+    const int n = (int)slices.size();
+    if (n > 65535) throw py::value_error("more slices than one launch takes (65535)");
+    int bad = 0;
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      TestStream ts;
+      DeviceSlices in(slices, ts.s);
+      gpu::DeviceBuffer flag(16);
+      HIP_CHECK(hipMemsetAsync(flag.as(), 0, 16, ts.s));
+      gpu::launch_check_fixed(in.descs.as<gpu::RunDesc>(), n, forced >= 0 ? forced : in.largest, flag.as<int>(), ts.s);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipMemcpyAsync(&bad, flag.as(), sizeof(bad), hipMemcpyDeviceToHost, ts.s));
+      HIP_CHECK(hipStreamSynchronize(ts.s));
+    }
+    return bad == 0;
+  }, py::arg("slices"), py::arg("max_nrec") = py::none(), py::arg("device") = 0);
+  // launch_count_mismatch: `start` plus the number of positions where the two word lists differ.
+  m.def("gpu_count_mismatch", [](const std::vector<uint64_t>& a, const std::vector<uint64_t>& b, uint64_t start,
+                                 int device) {
+    if (a.size() != b.size()) throw py::value_error("gpu_count_mismatch: the lists differ in length");
+    if (a.size() > (size_t)INT32_MAX) throw py::value_error("gpu_count_mismatch: too long");
+    unsigned long long errors = start;
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      TestStream ts;
+      const size_t bytes = a.size() * 8;
+      gpu::DeviceBuffer da(std::max<size_t>(bytes, 16)), db(std::max<size_t>(bytes, 16)), de(16);
+      if (bytes) {
+        HIP_CHECK(hipMemcpyAsync(da.as(), a.data(), bytes, hipMemcpyHostToDevice, ts.s));
+        HIP_CHECK(hipMemcpyAsync(db.as(), b.data(), bytes, hipMemcpyHostToDevice, ts.s));
+      }
+      HIP_CHECK(hipMemcpyAsync(de.as(), &errors, 8, hipMemcpyHostToDevice, ts.s));
+      gpu::launch_count_mismatch(da.as<unsigned long long>(), db.as<unsigned long long>(), (int)a.size(),
+                                 de.as<unsigned long long>(), ts.s);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipMemcpyAsync(&errors, de.as(), 8, hipMemcpyDeviceToHost, ts.s));
+      HIP_CHECK(hipStreamSynchronize(ts.s));
+    }
+    return (uint64_t)errors;
+  }, py::arg("a"), py::arg("b"), py::arg("start") = 0, py::arg("device") = 0);
+  // The contract of sorted generation (kernels.h): raises ValueError when a run's key span is below its
+  // record count. No device needed.
+  m.def("teragen_require_spans", [](const std::vector<int64_t>& nrec, const std::vector<uint64_t>& key_span) {
+    if (nrec.size() != key_span.size()) throw py::value_error("teragen_require_spans: one span per run");
+    gpu::require_teragen_spans(nrec.data(), key_span.data(), (int)nrec.size());
+  }, py::arg("nrec"), py::arg("key_span"));
+  // launch_teragen of all the runs in one launch. Every run's buffer is 104 * n + 2 bytes and 16 guard bytes
+  // behind them, all a5 before the launch; returns the buffers whole (guards included) and the checksums.
+  m.def("gpu_teragen", [](const std::vector<int64_t>& nrec, const std::vector<uint64_t>& key_lo,
+                          const std::vector<uint64_t>& key_span, const std::vector<uint64_t>& seeds, bool unsorted,
+                          int device) {
+    const size_t R = nrec.size();
+    if (key_lo.size() != R || key_span.size() != R || seeds.size() != R)
+      throw py::value_error("gpu_teragen: one key_lo, key_span and seed per run");
+    if (R > 65535) throw py::value_error("gpu_teragen: more runs than one launch takes (65535)");
+    constexpr size_t kGuard = 16;
+    std::vector<size_t> at(R), len(R);
+    size_t total = 0;
+    int64_t max_n = 0;
+    for (size_t r = 0; r < R; ++r) {
+      if (nrec[r] < 0 || nrec[r] > (1 << 24)) throw py::value_error("gpu_teragen: nrec out of range");
+      at[r] = total;  // 16-byte aligned
+      len[r] = (size_t)nrec[r] * gpu::kTeraRecordBytes + 2 + kGuard;
+      total = (total + len[r] + 15) & ~(size_t)15;
+      max_n = std::max(max_n, nrec[r]);
+    }
+    if (!unsorted) gpu::require_teragen_spans(nrec.data(), key_span.data(), (int)R);
+    std::vector<uint8_t> host(total);
+    std::vector<uint64_t> ck(R);
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      TestStream ts;
+      gpu::DeviceBuffer data(std::max<size_t>(total, 16)), args(std::max<size_t>(R * 48, 16));
+      std::vector<uint8_t*> bases(R);
+      for (size_t r = 0; r < R; ++r) bases[r] = data.as<uint8_t>() + at[r];
+      // args: bases, nrec, key_lo, key_span, seeds, checksums (R words each)
+      uint64_t* a = args.as<uint64_t>();
+      HIP_CHECK(hipMemsetAsync(data.as(), 0xA5, data.size(), ts.s));
+      if (R) {
+        HIP_CHECK(hipMemcpyAsync(a, bases.data(), R * 8, hipMemcpyHostToDevice, ts.s));
+        HIP_CHECK(hipMemcpyAsync(a + R, nrec.data(), R * 8, hipMemcpyHostToDevice, ts.s));
+        HIP_CHECK(hipMemcpyAsync(a + 2 * R, key_lo.data(), R * 8, hipMemcpyHostToDevice, ts.s));
+        HIP_CHECK(hipMemcpyAsync(a + 3 * R, key_span.data(), R * 8, hipMemcpyHostToDevice, ts.s));
+        HIP_CHECK(hipMemcpyAsync(a + 4 * R, seeds.data(), R * 8, hipMemcpyHostToDevice, ts.s));
+        HIP_CHECK(hipMemsetAsync(a + 5 * R, 0, R * 8, ts.s));
+      }
+      gpu::launch_teragen(reinterpret_cast<uint8_t* const*>(a), reinterpret_cast<const int64_t*>(a + R), a + 2 * R,
+                          a + 3 * R, a + 4 * R, (int)R, max_n, reinterpret_cast<unsigned long long*>(a + 5 * R), ts.s,
+                          unsorted ? 1 : 0);
+      HIP_CHECK(hipGetLastError());
+      if (total) HIP_CHECK(hipMemcpyAsync(host.data(), data.as(), total, hipMemcpyDeviceToHost, ts.s));
+      if (R) HIP_CHECK(hipMemcpyAsync(ck.data(), a + 5 * R, R * 8, hipMemcpyDeviceToHost, ts.s));
+      HIP_CHECK(hipStreamSynchronize(ts.s));
+    }
+    py::list runs;
+    for (size_t r = 0; r < R; ++r) runs.append(py::bytes(reinterpret_cast<const char*>(host.data()) + at[r], len[r]));
+    return py::make_tuple(runs, ck);
+  }, py::arg("nrec"), py::arg("key_lo"), py::arg("key_span"), py::arg("seeds"), py::arg("unsorted") = false,
+        py::arg("device") = 0);
   // The constants of the block decode kernels (kernels.h: DecodeGeometry), for tests that place tokens on
   // their boundaries. Plain numbers: callable without a device.
   m.def("gpu_decode_geometry", [] {
