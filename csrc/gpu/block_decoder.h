@@ -28,7 +28,8 @@ struct BlockPlan {
 // not part of any block), none left is a stream without one (0), one to three are malformed as before.
 // So a trailer-less stream ending in a zero-length block (00 00 00 00) reads as a stream with the
 // checksum 0, the CRC of no bytes; block_compress never writes one, Hadoop only for an empty stream,
-// which an IFile partition never is. Null keeps the walk that knows no trailer.
+// which an IFile partition never is. Four trailing zero bytes are thus a trailer, never a block, to the host
+// walk and to the device walk alike (tests/test_gpu_frame_streams.py). Null keeps the walk that knows no trailer.
 bool plan_block_streams(Codec codec, const std::vector<const uint8_t*>& ptrs, const std::vector<int64_t>& lens,
                         BlockPlan* plan, std::vector<int>* tails = nullptr);
 

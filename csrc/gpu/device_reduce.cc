@@ -18,6 +18,7 @@
 #include <thread>
 
 #include "block_decoder.h"
+#include "block_rounds.h"
 #include "codec/colpack.h"
 #include "device_engine.h"
 #include "fixed_delivery.h"
@@ -628,10 +629,10 @@ DeviceReduceStats device_reduce_fixed(const DeviceReduceConfig& cfg, const std::
 namespace uda {
 namespace gpu {
 
-namespace {
-int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-bool key_less(const Elem& a, const Elem& b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
-}  // namespace
+// block_rounds.h cannot include kernels.h (no HIP there): its copies of the record geometry
+static_assert(kBlockRecordBytes == kTeraRecordBytes && kBlockKeyEnd == kTeraKeyOffset + kTeraKeyBytes,
+              "block_rounds.h and kernels.h disagree on the record");
+static_assert(kBlockKeyEnd <= kDecodePrefixSlot - (kTeraRecordBytes - 1), "a block's first key lies in its prefix slot");
 
 // Streaming decode (F6 per key-range round) of block-compressed FIXED10 partitions.
 //
@@ -685,16 +686,19 @@ DeviceReduceStats device_reduce_fixed_blocks(const DeviceReduceConfig& cfg, int 
   WsLease lease(cfg.device, N * kTeraRecordBytes);
   FixedWs& ws = *lease.w;
   hipStream_t s = ws.s;
-  std::vector<int32_t> first(NB, -1);
+  BlockGeometry geo;
+  geo.nrec = nrec;
+  geo.blk0 = blk0;
+  geo.rel.resize((size_t)NB);
+  geo.raw.resize((size_t)NB);
   std::vector<DecodeDesc> pd(plan.descs);
   for (int k = 0; k < K; ++k)
     for (int64_t b = blk0[k]; b < blk0[k + 1]; ++b) {
-      const int64_t rel = R(b, k);
-      const int64_t f = (kTeraRecordBytes - rel % kTeraRecordBytes) % kTeraRecordBytes;
-      if (rel + f + kTeraRecordBytes <= nrec[k] * kTeraRecordBytes && f + kTeraKeyOffset + kTeraKeyBytes <= pd[(size_t)b].raw)
-        first[(size_t)b] = (int32_t)f;
+      geo.rel[(size_t)b] = R(b, k);
+      geo.raw[(size_t)b] = pd[(size_t)b].raw;
       pd[(size_t)b].dst = b * kSlot;
     }
+  const std::vector<int32_t> first = block_first_offsets(geo);
   if (NB > 0) {
     FixedWs::ensure(ws.prefix, (size_t)NB * kSlot);
     FixedWs::ensure(ws.d_first, (size_t)NB * 4);
@@ -723,19 +727,15 @@ DeviceReduceStats device_reduce_fixed_blocks(const DeviceReduceConfig& cfg, int 
     return st;
   }
   // per stream: the blocks where a record starts, with its key (ascending in a sorted run)
-  std::vector<std::vector<std::pair<int64_t, Elem>>> idx(K);
-  std::vector<Elem> samp;
-  for (int k = 0; k < K; ++k)
-    for (int64_t b = blk0[k]; b < blk0[k + 1]; ++b)
-      if (first[(size_t)b] >= 0) {
-        if (!idx[k].empty() && key_less(keys[(size_t)b], idx[k].back().second)) {  // not a sorted run
-          lease.clean = true;
-          return st;
-        }
-        idx[k].emplace_back(b, keys[(size_t)b]);
-        samp.push_back(keys[(size_t)b]);
-      }
-  std::sort(samp.begin(), samp.end(), key_less);
+  BlockIndex index;
+  {
+    std::vector<BlockKey> bk((size_t)NB);
+    for (int64_t b = 0; b < NB; ++b) bk[(size_t)b] = BlockKey{keys[(size_t)b].hi, keys[(size_t)b].lo};
+    if (!build_block_index(geo, first, bk, &index)) {  // not a sorted run
+      lease.clean = true;
+      return st;
+    }
+  }
   *streamed = true;
   auto emit_eof_only = [&] {
     uint8_t eof[2] = {0xFF, 0xFF};
@@ -751,58 +751,15 @@ DeviceReduceStats device_reduce_fixed_blocks(const DeviceReduceConfig& cfg, int 
   const FixedLayout lay = fixed_layout(cfg.kv_buf_bytes, cfg.piece_bytes, cfg.pinned_slots, cfg.pack_version);
   HbmLedger& led = HbmLedger::get();
   int64_t round_bytes = std::max<int64_t>(cfg.round_bytes, kTeraRecordBytes);
-  struct Span {
-    int64_t b0 = 0, b1 = -1;        // blocks [b0, b1]
-    int64_t rec0 = 0, rec1 = 0;     // whole records inside, stream record indices
-    int64_t in_off = 0;             // decoded byte R(b0) lands here in the round input
-  };
-  int Q = 1;
+  RoundPlan rp;
+  int& Q = rp.Q;
+  const std::vector<std::vector<RoundSpan>>& spans = rp.spans;
+  const std::vector<int64_t>&in_bytes = rp.in_bytes, &in_recs = rp.in_recs;
   std::vector<Elem> bounds;
-  std::vector<std::vector<Span>> spans;
-  std::vector<int64_t> in_bytes, in_recs;
   auto plan_rounds = [&](int64_t rb) {
-    Q = (int)std::max<int64_t>(1, (N * kTeraRecordBytes + rb - 1) / rb);
-    bounds.assign((size_t)std::max(0, Q - 1), Elem{0, 0});
-    for (int q = 1; q < Q; ++q) bounds[(size_t)q - 1] = samp.empty() ? Elem{~0ull, ~0ull} : samp[samp.size() * (size_t)q / (size_t)Q];
-    spans.assign((size_t)Q, std::vector<Span>((size_t)K));
-    in_bytes.assign((size_t)Q, 0);
-    in_recs.assign((size_t)Q, 0);
-    for (int q = 0; q < Q; ++q) {
-      int64_t cur = 0;
-      for (int k = 0; k < K; ++k) {
-        Span& sp = spans[(size_t)q][(size_t)k];
-        if (nrec[k] == 0 || blk0[k] == blk0[k + 1]) continue;
-        const auto& ix = idx[k];
-        // b0: the last block starting a record with a key below the low bound (round 0: the first block)
-        sp.b0 = blk0[k];
-        if (q > 0) {
-          const Elem lo = bounds[(size_t)q - 1];
-          auto it = std::lower_bound(ix.begin(), ix.end(), lo, [](const std::pair<int64_t, Elem>& a, const Elem& v) {
-            return key_less(a.second, v);
-          });
-          if (it != ix.begin()) sp.b0 = std::prev(it)->first;
-        }
-        // b1: the first block starting a record with a key at or above the high bound (last round: the last block)
-        sp.b1 = blk0[k + 1] - 1;
-        if (q + 1 < Q) {
-          const Elem hi = bounds[(size_t)q];
-          auto it = std::lower_bound(ix.begin(), ix.end(), hi, [](const std::pair<int64_t, Elem>& a, const Elem& v) {
-            return key_less(a.second, v);
-          });
-          if (it != ix.end()) sp.b1 = it->first;
-        }
-        if (sp.b1 < sp.b0) sp.b1 = sp.b0;
-        const int64_t r0 = R(sp.b0, k), r1 = R(sp.b1, k) + plan.descs[(size_t)sp.b1].raw;
-        sp.rec0 = (r0 + kTeraRecordBytes - 1) / kTeraRecordBytes;
-        sp.rec1 = std::min(r1 / kTeraRecordBytes, nrec[k]);
-        if (sp.rec1 < sp.rec0) sp.rec1 = sp.rec0;
-        const int64_t lead = sp.rec0 * kTeraRecordBytes - r0;  // partial record before the first whole one
-        sp.in_off = align_up(cur + lead, 16) - lead;            // record starts 16-byte aligned
-        cur = sp.in_off + (r1 - r0);
-        in_recs[(size_t)q] += sp.rec1 - sp.rec0;
-      }
-      in_bytes[(size_t)q] = align_up(cur, 256);
-    }
+    gpu::plan_rounds(geo, index, rb, &rp);
+    bounds.resize(rp.bounds.size());
+    for (size_t i = 0; i < bounds.size(); ++i) bounds[i] = Elem{rp.bounds[i].hi, rp.bounds[i].lo};
   };
   auto need = [&](int64_t rb) {
     plan_rounds(rb);
@@ -872,7 +829,7 @@ DeviceReduceStats device_reduce_fixed_blocks(const DeviceReduceConfig& cfg, int 
     std::vector<uint8_t*> bases((size_t)K, in);
     std::vector<int64_t> n((size_t)K, 0);
     for (int k = 0; k < K; ++k) {
-      const Span& sp = spans[(size_t)q][(size_t)k];
+      const RoundSpan& sp = spans[(size_t)q][(size_t)k];
       if (sp.b1 < sp.b0 || nrec[k] == 0) continue;
       const int64_t r0 = R(sp.b0, k);
       for (int64_t b = sp.b0; b <= sp.b1; ++b) {

@@ -18,6 +18,7 @@
 #include <random>
 
 #include "block_decoder.h"
+#include "block_rounds.h"
 #include "device_engine.h"
 #include "device_ptr.h"
 #include "device_reduce.h"
@@ -262,6 +263,71 @@ py::bytes cpu_merge_impl(const std::vector<std::string>& runs, const std::string
     lens->push_back(len);
   }
   return py::bytes(out);
+}
+
+// A block plan as Python sees it: ([(stream, src, src_end, dst, raw)], raw_offset, tails), src and src_end
+// as offsets into the block's own stream. `base` is what the descriptors' src counts from (0: the streams
+// back to back in one host buffer; a device address: the same layout in device memory).
+py::tuple block_plan_tuple(const gpu::BlockPlan& plan, const std::vector<int64_t>& lens, int64_t base,
+                           const std::vector<int>& tails, bool with_tails) {
+  std::vector<int64_t> at(lens.size() + 1, 0);
+  for (size_t i = 0; i < lens.size(); ++i) at[i + 1] = at[i] + lens[i];
+  py::list descs;
+  size_t k = 0;
+  for (const auto& d : plan.descs) {
+    // a stream's blocks are those with dst in [raw_offset[k], raw_offset[k + 1]) (every block has raw > 0)
+    while (k + 1 < lens.size() && d.dst >= plan.raw_offset[k + 1]) ++k;
+    descs.append(py::make_tuple((int64_t)k, d.src - base - at[k], d.src_end - base - at[k], d.dst, d.raw));
+  }
+  py::list ro, tl;
+  for (int64_t v : plan.raw_offset) ro.append(v);
+  if (with_tails)
+    for (int v : tails) tl.append(v);
+  return py::make_tuple(descs, ro, tl);
+}
+
+constexpr int64_t kStreamGuard = 256;
+
+// The streams back to back in one device buffer (no alignment between them, as partitions lie in a MOF)
+// with kStreamGuard bytes of 0xA5 behind the last.
+void upload_streams(const std::vector<std::string>& streams, gpu::DeviceBuffer* buf, std::vector<const uint8_t*>* dptrs,
+                    std::vector<int64_t>* lens) {
+  std::string all;
+  for (const auto& st : streams) all += st;
+  all.append((size_t)kStreamGuard, (char)0xA5);
+  buf->alloc(all.size());
+  HIP_CHECK(hipMemcpy(buf->as(), all.data(), all.size(), hipMemcpyHostToDevice));
+  size_t off = 0;
+  for (const auto& st : streams) {
+    dptrs->push_back(buf->as<uint8_t>() + off);
+    lens->push_back((int64_t)st.size());
+    off += st.size();
+  }
+}
+
+void check_stream_guard(const gpu::DeviceBuffer& buf, const std::vector<int64_t>& lens) {
+  int64_t data = 0;
+  for (int64_t l : lens) data += l;
+  std::string g((size_t)kStreamGuard, '\0');
+  HIP_CHECK(hipMemcpy(&g[0], buf.as<uint8_t>() + data, g.size(), hipMemcpyDeviceToHost));
+  for (char c : g)
+    if ((uint8_t)c != 0xA5) throw UdaError("the guard bytes behind the compressed streams changed");
+}
+
+gpu::BlockKey block_key_of(const std::string& k) {
+  if (k.size() != 10) throw py::value_error("a key is 10 bytes");
+  gpu::BlockKey v;
+  for (int i = 0; i < 8; ++i) v.hi = (v.hi << 8) | (uint8_t)k[(size_t)i];
+  v.lo = (((uint64_t)(uint8_t)k[8] << 8) | (uint8_t)k[9]) << 48;
+  return v;
+}
+
+py::bytes block_key_bytes(const gpu::BlockKey& v) {
+  char k[10];
+  for (int i = 0; i < 8; ++i) k[i] = (char)(v.hi >> (56 - 8 * i));
+  k[8] = (char)(v.lo >> 56);
+  k[9] = (char)(v.lo >> 48);
+  return py::bytes(k, 10);
 }
 
 }  // namespace
@@ -628,6 +694,70 @@ PYBIND11_MODULE(_uda_native, m) {
     return py::make_tuple(bufs, d);
   }, py::arg("runs"), py::arg("kv_buf"), py::arg("round_bytes"), py::arg("piece_bytes") = 64ll << 20,
      py::arg("pack") = "auto", py::arg("device") = 0);
+  // Upload block-compressed FIXED10 partitions back to back (followed by a guard), walk their framing on
+  // the device and run device_reduce_fixed_blocks over the plan. Returns (buffers, stats); stats["streamed"]
+  // False: nothing was delivered (the caller of the C++ function decodes the partitions whole). trailers:
+  // every stream may end in an IFile checksum.
+  m.def("gpu_device_reduce_fixed_blocks", [](int codec, const std::vector<std::string>& streams, int64_t kv_buf,
+                                             int64_t round_bytes, int64_t piece_bytes, const std::string& pack,
+                                             int device, bool trailers) {
+    gpu::DeviceReduceConfig cfg;
+    cfg.device = device;
+    cfg.kv_buf_bytes = kv_buf;
+    cfg.round_bytes = round_bytes;
+    cfg.piece_bytes = piece_bytes;
+    cfg.pack_version = gpu::delivery_pack_version(pack);
+    if (cfg.pack_version < 0) throw py::value_error("gpu_device_reduce_fixed_blocks: pack is auto, v1 or off");
+    if (kv_buf < 1 || round_bytes < 1 || piece_bytes < 1) throw py::value_error("gpu_device_reduce_fixed_blocks: bad sizes");
+    if (codec < 1 || codec > 3) throw py::value_error("gpu_device_reduce_fixed_blocks: codec is 1 (snappy), 2 (lzo) or 3 (lz4)");
+    std::vector<std::string> out;
+    gpu::DeviceReduceStats st;
+    bool streamed = false;
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      gpu::DeviceBuffer din, scratch, desc_scratch;
+      std::vector<const uint8_t*> dptrs;
+      std::vector<int64_t> lens;
+      upload_streams(streams, &din, &dptrs, &lens);
+      gpu::BlockPlan plan;
+      std::vector<int> tl;
+      hipStream_t s;
+      HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      bool ok = false;
+      try {
+        ok = gpu::plan_block_streams_device((Codec)codec, dptrs, lens, &plan, scratch, desc_scratch, s, trailers ? &tl : nullptr);
+      } catch (...) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+        throw;
+      }
+      HIP_CHECK(hipStreamDestroy(s));
+      if (!ok) throw UdaError("block framing not resolvable on the device");
+      st = gpu::device_reduce_fixed_blocks(cfg, codec, plan, [&](const uint8_t* b, int64_t len) {
+        out.emplace_back((const char*)b, (size_t)len);
+        return 0;
+      }, &streamed);
+      check_stream_guard(din, lens);
+    }
+    py::list bufs;
+    for (const auto& b : out) bufs.append(py::bytes(b));
+    py::dict d;
+    d["streamed"] = streamed;
+    d["records"] = st.records;
+    d["bytes"] = st.bytes;
+    d["buffers"] = st.buffers;
+    d["rounds"] = st.rounds;
+    d["round_bytes"] = st.round_bytes;
+    d["decoded_blocks"] = st.decoded_blocks;
+    d["d2h_bytes"] = st.d2h_bytes;
+    d["pieces"] = st.pieces;
+    d["packed_pieces"] = st.packed_pieces;
+    d["raw_pieces"] = st.raw_pieces;
+    d["delta_pieces"] = st.delta_pieces;
+    return py::make_tuple(bufs, d);
+  }, py::arg("codec"), py::arg("streams"), py::arg("kv_buf"), py::arg("round_bytes"), py::arg("piece_bytes") = 64ll << 20,
+     py::arg("pack") = "auto", py::arg("device") = 0, py::arg("trailers") = false);
   // Merge given sorted FIXED10 runs (whole 104-byte records, no EOF marker) with a DeviceMerger made for
   // this call, so the UDA_KWAY* environment of the moment applies. The runs share one device buffer; each
   // starts at a multiple of 16 bytes plus `pad` (8: the staged kernel's half-chunk offset; 2: the
@@ -742,6 +872,118 @@ PYBIND11_MODULE(_uda_native, m) {
       throw py::value_error("block framing malformed or not resolvable without decoding");
     return py::make_tuple((int64_t)plan.descs.size(), tails[0]);
   }, py::arg("codec"), py::arg("stream"));
+  // the host walk of several streams in full: ([(stream, src, src_end, dst, raw) per block], raw_offset,
+  // tails), src and src_end as offsets into the block's stream; None when the framing is not resolvable
+  m.def("plan_block_streams_descs", [](int codec, const std::vector<std::string>& streams, bool tails) -> py::object {
+    std::vector<const uint8_t*> ptrs;
+    std::vector<int64_t> lens;
+    for (const auto& st : streams) {
+      ptrs.push_back((const uint8_t*)st.data());
+      lens.push_back((int64_t)st.size());
+    }
+    gpu::BlockPlan plan;
+    std::vector<int> tl;
+    if (!gpu::plan_block_streams((Codec)codec, ptrs, lens, &plan, tails ? &tl : nullptr)) return py::none();
+    return block_plan_tuple(plan, lens, 0, tl, tails);
+  }, py::arg("codec"), py::arg("streams"), py::arg("tails") = false);
+  // the device walk (plan_block_streams_device) of the same streams, uploaded back to back without
+  // alignment and followed by a guard; the same tuple, or None
+  m.def("gpu_plan_block_streams_device", [](int codec, const std::vector<std::string>& streams, bool tails,
+                                            int device) -> py::object {
+    gpu::BlockPlan plan;
+    std::vector<int> tl;
+    std::vector<int64_t> lens;
+    bool ok = false;
+    int64_t base = 0;
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      gpu::DeviceBuffer din, scratch, desc_scratch;
+      std::vector<const uint8_t*> dptrs;
+      upload_streams(streams, &din, &dptrs, &lens);
+      base = (int64_t)(uintptr_t)din.as<uint8_t>();
+      hipStream_t s;
+      HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      try {
+        ok = gpu::plan_block_streams_device((Codec)codec, dptrs, lens, &plan, scratch, desc_scratch, s, tails ? &tl : nullptr);
+      } catch (...) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+        throw;
+      }
+      HIP_CHECK(hipStreamDestroy(s));
+      check_stream_guard(din, lens);
+    }
+    if (!ok) return py::none();
+    return block_plan_tuple(plan, lens, base, tl, tails);
+  }, py::arg("codec"), py::arg("streams"), py::arg("tails") = false, py::arg("device") = 0);
+  // The round plan of the streaming block decode (block_rounds.h), no device needed. nrec: records per
+  // stream; blocks: per stream the raw sizes of its non-empty blocks; first_keys: per block (all streams, in
+  // order) the 10 key bytes of the first record that starts in it, or None where there is none (only the
+  // entries of blocks whose `first` is >= 0 are read). Returns {first, sorted, Q, bounds, spans, in_bytes,
+  // in_recs}; spans[q][k] = {b0, b1, rec0, rec1, in_off}, blocks numbered over all streams. sorted False
+  // (the keys of a stream descend): no rounds are planned.
+  m.def("block_round_plan", [](const std::vector<int64_t>& nrec, const std::vector<std::vector<int64_t>>& blocks,
+                               const std::vector<py::object>& first_keys, int64_t round_bytes) {
+    if (nrec.size() != blocks.size()) throw py::value_error("block_round_plan: one block list per stream");
+    if (round_bytes < 1) throw py::value_error("block_round_plan: round_bytes < 1");
+    gpu::BlockGeometry g;
+    g.nrec = nrec;
+    g.blk0.push_back(0);
+    for (size_t k = 0; k < blocks.size(); ++k) {
+      int64_t rel = 0;
+      for (int64_t raw : blocks[k]) {
+        if (raw < 1) throw py::value_error("block_round_plan: a block holds at least one byte");
+        g.rel.push_back(rel);
+        g.raw.push_back(raw);
+        rel += raw;
+      }
+      if (nrec[k] < 0 || rel != nrec[k] * gpu::kBlockRecordBytes + 2)
+        throw py::value_error("block_round_plan: a stream's blocks hold its records and the EOF marker");
+      g.blk0.push_back((int64_t)g.rel.size());
+    }
+    if (first_keys.size() != g.rel.size()) throw py::value_error("block_round_plan: one first key (or None) per block");
+    const std::vector<int32_t> first = gpu::block_first_offsets(g);
+    std::vector<gpu::BlockKey> keys(first.size(), gpu::BlockKey{~0ull, ~0ull});
+    for (size_t b = 0; b < first.size(); ++b)
+      if (first[b] >= 0) {
+        if (first_keys[b].is_none()) throw py::value_error("block_round_plan: a block that starts a record needs its key");
+        keys[b] = block_key_of(first_keys[b].cast<std::string>());
+      }
+    py::dict d;
+    py::list fl;
+    for (int32_t f : first) fl.append((int)f);
+    d["first"] = fl;
+    gpu::BlockIndex index;
+    const bool sorted = gpu::build_block_index(g, first, keys, &index);
+    d["sorted"] = sorted;
+    if (!sorted) return d;
+    gpu::RoundPlan rp;
+    gpu::plan_rounds(g, index, round_bytes, &rp);
+    d["Q"] = rp.Q;
+    py::list bounds, spans, ib, ir;
+    for (const auto& b : rp.bounds) bounds.append(block_key_bytes(b));
+    for (int q = 0; q < rp.Q; ++q) {
+      py::list row;
+      for (const auto& sp : rp.spans[(size_t)q]) {
+        py::dict e;
+        e["b0"] = sp.b0;
+        e["b1"] = sp.b1;
+        e["rec0"] = sp.rec0;
+        e["rec1"] = sp.rec1;
+        e["in_off"] = sp.in_off;
+        row.append(e);
+      }
+      spans.append(row);
+      ib.append(rp.in_bytes[(size_t)q]);
+      ir.append(rp.in_recs[(size_t)q]);
+    }
+    d["bounds"] = bounds;
+    d["spans"] = spans;
+    d["in_bytes"] = ib;
+    d["in_recs"] = ir;
+    return d;
+  }, py::arg("nrec"), py::arg("blocks"), py::arg("first_keys"), py::arg("round_bytes"));
   m.def("gpu_crc32_chunk_bytes", [] { return gpu::crc32_chunk_bytes(); });
   // zlib.crc32 of every input by one launch of the device kernels (crc32.hip): the inputs lie in one device
   // buffer, each at an address that is `misalign` modulo 16
