@@ -349,7 +349,8 @@ def hybrid_budget(args) -> dict:
     the device at --budget-gb and mapred.uda.gpu.merge.bytes at --merge-gb, so the task takes the GPU
     hybrid merge (direct RPQ key-range rounds over the fetched partitions; the reference's LPQ/RPQ,
     src/Merger/MergeManager.cc:202-288). The stream is validated natively (framing, key order, record
-    checksum against the generated runs)."""
+    checksum against the generated runs). --ifile-checksum skip | verify: the MOFs carry Hadoop's IFile checksum
+    trailer and mapred.uda.ifile.checksum.over.budget is set to that value (none: no trailers, the key absent)."""
     import resource
     from uda_amd import native
     from uda_amd.bridge import UdaConsumer, UdaProvider
@@ -357,13 +358,14 @@ def hybrid_budget(args) -> dict:
     from uda_amd.utils.mof import encode_partitions
     n = native()
     rows = int(args.gb * 1e9 / 100 / args.maps)
+    trailers = args.ifile_checksum != "none"
     prov = UdaProvider()
     total, want_sum = 0, 0
     for m in range(args.maps):  # one map at a time: the host holds the encoded MOFs, not the runs too
         parts = n.generate_runs("secondary", 1, 1, rows, 1000 + m)[0]
         want_sum = (want_sum + n.ifile_checksum(parts[0])[2]) & 0xFFFFFFFFFFFFFFFF
-        data, index = encode_partitions(parts)
-        total += len(data) - 2
+        data, index = encode_partitions(parts, None, checksum=trailers)
+        total += len(data) - 2 - (4 if trailers else 0)
         prov.add_mof_memory("job_hb", f"attempt_hb_m_{m:06d}_0", data, index)
         del parts
         if m % 8 == 7:  # progress (a GPU box takes a silent minute for a hung run)
@@ -371,6 +373,8 @@ def hybrid_budget(args) -> dict:
     budget = int(args.budget_gb * 1e9)
     conf = {"mapred.uda.merge.backend": "gpu", "mapred.uda.gpu.hbm.budget": budget,
             "mapred.uda.gpu.merge.bytes": int(args.merge_gb * 1e9), "mapred.uda.gpu.spill": "host"}
+    if trailers:
+        conf["mapred.uda.ifile.checksum.over.budget"] = args.ifile_checksum
     c = UdaConsumer(args.maps, "job_hb", "attempt_hb_r_000000_0", TEXT, conf=conf, keep_records=False, validate=True)
     t0 = time.perf_counter()
     for m in range(args.maps):
@@ -391,6 +395,9 @@ def hybrid_budget(args) -> dict:
            "rpq_rounds": st.get("rpq_rounds"), "lpqs": st.get("lpqs"), "delivered_ok": st["bytes_delivered"] - 2 == total,
            "ledger_peak_gb": round(hs["peak"] / 1e9, 2), "device_peak_gb": round(hs["device_peak"] / 1e9, 2),
            "over_budget_bytes": hs["over"], "max_rss_gb": round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1e6, 1)}
+    if trailers:
+        out.update({k: st.get(k) for k in ("ifile_checksum", "checksum_partitions", "gpu_checksum_ms")})
+        out["ifile_checksum_over_budget"] = args.ifile_checksum
     out["validation"] = {"records": v.records, "order_errors": v.order_errors, "framing_errors": v.framing_errors,
                          "eof": v.eof, "checksum_ok": v.checksum == want_sum}
     out["validated"] = bool(v.order_errors == 0 and v.framing_errors == 0 and v.eof and v.checksum == want_sum
@@ -755,6 +762,9 @@ def main() -> int:
     ap.add_argument("--validate", action="store_true")
     ap.add_argument("--budget-gb", type=float, default=10.0, help="hybrid_budget: mapred.uda.gpu.hbm.budget")
     ap.add_argument("--merge-gb", type=float, default=8.0, help="hybrid_budget: mapred.uda.gpu.merge.bytes")
+    ap.add_argument("--ifile-checksum", default="none", choices=["none", "skip", "verify"],
+                    help="hybrid_budget: MOFs with IFile checksum trailers under "
+                         "mapred.uda.ifile.checksum.over.budget=skip | verify (none: no trailers)")
     ap.add_argument("--vocab", type=int, default=0,
                     help="combine: words drawn uniformly from this many (default: the Zipf generator's 100 000)")
     ap.add_argument("--tasks", type=int, default=0, help="combine: concurrent reduce tasks (default 16)")

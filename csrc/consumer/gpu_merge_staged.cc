@@ -29,6 +29,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <future>
 #include <memory>
 #include <mutex>
@@ -89,6 +90,54 @@ struct DirectPlan {
   bool planned_all = false;
   int64_t target = 0;
   int epoch = 0;
+  std::vector<char> eof;        // runs[k].bytes is final: the run is indexed to its EOF marker
+};
+
+// mapred.uda.ifile.checksum.over.budget=verify over direct RPQ rounds: the partitions never lie whole in HBM,
+// but a run's slices are contiguous over the rounds (slice_rounds: b[k][q] to b[k][q + 1]), so every body
+// byte passes through HBM once, in order. Each round's device_merge leaves one raw CRC state per slice
+// (ChecksumPolicy::slice_states); the delivering thread folds a run's states in round order and compares
+// with the stored value once the run's body is complete. Runs without a trailer are not folded.
+class SliceChecksums {
+ public:
+  void add_run(bool trailer, int64_t body, const std::string& map_id) {
+    runs_.push_back(Run{trailer, !trailer, body, map_id, Crc32Running()});
+    any_ = any_ || trailer;
+  }
+  bool any() const { return any_; }
+  size_t size() const { return runs_.size(); }
+  bool open(size_t k) const { return !runs_[k].closed; }
+  int64_t folded(size_t k) const { return runs_[k].crc.bytes(); }
+  // slice [b, e) of run k went through HBM with state `st`; bytes between the last slice and this one (none,
+  // as the rounds are planned) are folded on the host from the pinned partition at mem
+  void fold(size_t k, const uint8_t* mem, int64_t b, int64_t e, uint32_t st) {
+    Run& r = runs_[k];
+    if (b < r.crc.bytes() || e < b || e > r.body)
+      throw UdaError("RPQ slice [" + std::to_string(b) + ", " + std::to_string(e) + ") of map output " + r.map_id +
+                     " does not follow the " + std::to_string(r.crc.bytes()) + " bytes checksummed so far");
+    if (b > r.crc.bytes()) r.crc.append_bytes(mem + r.crc.bytes(), (size_t)(b - r.crc.bytes()));
+    r.crc.append_state(st, e - b);
+  }
+  // The run's last slice is in: the body bytes no slice carries (the EOF marker, which the run's index leaves
+  // out) from the host copy, then the comparison with the trailer behind the body. Returns the body's length.
+  int64_t close(size_t k, const uint8_t* mem) {
+    Run& r = runs_[k];
+    r.crc.append_bytes(mem + r.crc.bytes(), (size_t)(r.body - r.crc.bytes()));
+    r.closed = true;
+    const uint32_t stored = ifile_stored_checksum(mem + r.body), got = r.crc.value();
+    if (stored != got) throw UdaError(ifile_checksum_mismatch(r.map_id, stored, got, r.body));
+    return r.body;
+  }
+
+ private:
+  struct Run {
+    bool trailer, closed;
+    int64_t body;
+    std::string map_id;
+    Crc32Running crc;
+  };
+  std::vector<Run> runs_;
+  bool any_ = false;
 };
 
 }  // namespace
@@ -134,6 +183,8 @@ class StagedMerge {
   void read_run(const SpillRun& run, int64_t off, int64_t len, uint8_t* dst);
   std::vector<std::vector<int64_t>> run_bounds(const std::vector<std::string>& split);
   void open_pipeline(RpqPipeline* pipe);
+  void fold_slices(const RoundSlices& rr, const DeviceMergeOut& m, const std::vector<uint8_t*>& mems,
+                   const std::vector<int64_t>& fin, bool last, const std::function<void(size_t)>& landed);
   // end
   void cleanup(bool ok);
   void finish();
@@ -166,10 +217,17 @@ class StagedMerge {
   bool combine_skipped_ = false;
   // IFile checksum trailers (uda/ifile.h, mapred.uda.ifile.checksum): partitions whose trailer was stripped,
   // and of those verified on the device. The online and progressive merges verify every one; over budget
-  // (LPQ spills, RPQ rounds over partitions that never lie whole in HBM) they are stripped unverified.
+  // (LPQ spills, RPQ rounds over partitions that never lie whole in HBM) they are stripped unverified unless
+  // mapred.uda.ifile.checksum.over.budget=verify.
   std::atomic<int64_t> trailers_{0}, verified_{0};
   std::vector<std::string> map_ids_;  // Span::id -> map output, for the mismatch message
   ChecksumPolicy verify_ck_, strip_ck_;
+  // mapred.uda.ifile.checksum.over.budget=verify (under auto): the LPQ merges verify their groups (lpq_ck_ is
+  // verify_ck_, else strip_ck_), the direct RPQ rounds ask for slice states (slice_ck_) and slice_sums_ folds them
+  bool verify_over_ = false;
+  ChecksumPolicy lpq_ck_, slice_ck_;
+  SliceChecksums slice_sums_;
+  double slice_ms_ = 0;  // device CRC time of rounds not yet booked with a closed run
   // over budget under mapred.uda.merge.combine.over.budget=combine: the op of the RPQ rounds, and of the
   // LPQ merges (kNone under an LPQ checkpoint: its spills stay as a resumed attempt expects them)
   CombineOp hybrid_combine_ = CombineOp::kNone, lpq_combine_ = CombineOp::kNone;
@@ -353,6 +411,9 @@ void StagedMerge::read_conf() {
   ckpt_ = t_.checkpoint_ && tier_ == "disk";
   verify_ck_ = ChecksumPolicy{t_.checksum_ == ChecksumMode::kAuto, &map_ids_};
   strip_ck_ = ChecksumPolicy{false, &map_ids_};
+  verify_over_ = verify_ck_.verify && t_.checksum_over_budget_;
+  lpq_ck_ = verify_over_ ? verify_ck_ : strip_ck_;
+  slice_ck_ = ChecksumPolicy{false, &map_ids_, true};
   hybrid_combine_ = t_.combine_over_budget_ ? t_.combine_ : CombineOp::kNone;
   lpq_combine_ = ckpt_ ? CombineOp::kNone : hybrid_combine_;
   // Progressive phases (ProgFetch). Default (-1): 4 phases when the task is the only staged GPU merge on
@@ -517,6 +578,7 @@ void StagedMerge::start_direct_prog(const std::vector<std::shared_ptr<MofFetcher
     dp.cap.push_back(cap);
     dp.body.push_back(cap - tail);
     if (tail) ++trailers_;
+    if (verify_over_) slice_sums_.add_run(tail != 0, cap - tail, f->params().map_id);
   }
   const size_t K = (size_t)dp.K;
   // each partition's pinned span is taken by the thread that fetches its first phase (in parallel,
@@ -778,13 +840,13 @@ void StagedMerge::merge_spill(std::vector<Span> jg, std::vector<std::string> ids
   DeviceMergeOut m;
   try {
     m = device_merge(ws, jg, stage_codec_, t_.kind_, lpq_spacing(), s, nullptr, false, lpq_combine_, 256ll << 20,
-                     &strip_ck_);
+                     &lpq_ck_);
   } catch (const std::runtime_error& e) {
     // the merge's cuts are the index samples, and a cut spacing bounds the record size: a record longer than
     // the finer spacing of a combined spill takes the usual one
     if (lpq_spacing() == kSampleSpacing || !std::strstr(e.what(), "record larger than the delivery buffer")) throw;
     m = device_merge(ws, jg, stage_codec_, t_.kind_, kSampleSpacing, s, nullptr, false, lpq_combine_, 256ll << 20,
-                     &strip_ck_);
+                     &lpq_ck_);
   }
   count_checksums(m);
   if (lpq_combine_ != CombineOp::kNone) combine_in_ += m.records_in;
@@ -940,6 +1002,33 @@ void StagedMerge::open_pipeline(RpqPipeline* pipe) {
   pipe->s[2] = pipe->sg3.s;
 }
 
+// Round `rr` has merged (m: its slice states), and is not delivered yet: fold every open run's slice and
+// close the runs whose records are all in (fin[k]: the run's final length in records' bytes, -1 while it is
+// not known; last: no round follows). A mismatch throws here, so the round it is found in is not delivered;
+// earlier key ranges are. landed(k): called before run k's trailer is read.
+void StagedMerge::fold_slices(const RoundSlices& rr, const DeviceMergeOut& m, const std::vector<uint8_t*>& mems,
+                              const std::vector<int64_t>& fin, bool last, const std::function<void(size_t)>& landed) {
+  const size_t K = slice_sums_.size();
+  if (rr.size() != K || m.slice_crc.size() != K || mems.size() != K || fin.size() != K)
+    throw UdaError("RPQ round of " + std::to_string(rr.size()) + " slices with " + std::to_string(m.slice_crc.size()) +
+                   " checksum states for " + std::to_string(K) + " runs");
+  slice_ms_ += m.checksum_ms;
+  int64_t parts = 0, bytes = 0;
+  for (size_t k = 0; k < K; ++k) {
+    if (!slice_sums_.open(k)) continue;
+    slice_sums_.fold(k, mems[k], rr[k].first, rr[k].second, m.slice_crc[k]);
+    if (!last && (fin[k] < 0 || slice_sums_.folded(k) < fin[k])) continue;
+    if (landed) landed(k);
+    bytes += slice_sums_.close(k, mems[k]);
+    ++parts;
+  }
+  if (parts > 0) {
+    verified_ += parts;
+    t_.note_checksum(parts, bytes, slice_ms_);
+    slice_ms_ = 0;
+  }
+}
+
 // plan the rounds of every key range that has fully arrived; false while nothing new can be planned
 bool StagedMerge::plan_more(DirectPlan& pl, bool wait) {
   DirectProg& dp = *dprog_;
@@ -967,7 +1056,10 @@ bool StagedMerge::plan_more(DirectPlan& pl, bool wait) {
     }
     pl.taken[(size_t)k] = vc.size();
     r.bytes = dp.complete[(size_t)k];
-    if (dp.eof[(size_t)k]) continue;
+    if (dp.eof[(size_t)k]) {
+      pl.eof[(size_t)k] = 1;
+      continue;
+    }
     all_eof = false;
     if (dp.last_key[(size_t)k].empty()) {
       blocked = true;  // no complete record of this run yet: nothing below any bound is known
@@ -1003,10 +1095,12 @@ void StagedMerge::run_progressive_direct() {
   pl.runs.resize((size_t)K);
   pl.at.assign((size_t)K, 0);
   pl.taken.assign((size_t)K, 0);
+  pl.eof.assign((size_t)K, 0);
   pl.target = std::max<int64_t>(round_target(), dp.spacing);
   // three workspaces, two rounds prepared ahead (as the direct RPQ of run_hybrid)
   RpqPipeline pipe;
   open_pipeline(&pipe);
+  const ChecksumPolicy* const slice_ck = slice_sums_.any() ? &slice_ck_ : nullptr;
   // a round's slices by value: `rounds` grows (and reallocates) on this thread while earlier rounds merge
   auto prep = [&](size_t q, RoundSlices rr, std::vector<uint8_t*> mems) {
     if (hipSetDevice(device_) != hipSuccess) throw UdaError("hipSetDevice failed");
@@ -1014,8 +1108,18 @@ void StagedMerge::run_progressive_direct() {
     for (int k = 0; k < K; ++k)
       views[(size_t)k] = Span{mems[(size_t)k] + rr[(size_t)k].first, rr[(size_t)k].second - rr[(size_t)k].first};
     return device_merge(*pipe.ws[q % 3], views, Codec::kNone, t_.kind_, kv_, pipe.s[q % 3], nullptr, true,
-                        hybrid_combine_);
+                        hybrid_combine_, 256ll << 20, slice_ck);
   };
+  // a run's trailer may lie in a later phase than its EOF marker: it is compared once every phase is in
+  auto landed = [&](size_t k) {
+    std::unique_lock<std::mutex> lk(dp.mu);
+    while (!dp.cv.wait_for(lk, std::chrono::milliseconds(50),
+                           [&] { return dp.indexed[k] == dp.P || dp.err || t_.stop_; })) {
+    }
+    if (dp.err) std::rethrow_exception(dp.err);
+    if (t_.stop_) throw UdaError("reduce task stopped during fetch");
+  };
+  std::vector<int64_t> fin((size_t)K);
   std::vector<std::future<DeviceMergeOut>> next;
   // at most three rounds in flight (one delivering, two preparing): workspace q % 3 is free again
   // once round q - 3 has been delivered
@@ -1039,7 +1143,16 @@ void StagedMerge::run_progressive_direct() {
     DeviceMergeOut m = next[q].get();
     if (hybrid_combine_ != CombineOp::kNone) combine_in_ += m.records_in;
     issue(q);
-    deliver(m, pl.planned_all && q + 1 == pl.rounds.size(), pipe.s[q % 3], *pipe.ws[q % 3]);
+    const bool last = pl.planned_all && q + 1 == pl.rounds.size();
+    if (slice_ck) {
+      std::vector<uint8_t*> mems((size_t)K);
+      for (int k = 0; k < K; ++k) {
+        mems[(size_t)k] = pl.runs[(size_t)k].mem;
+        fin[(size_t)k] = pl.eof[(size_t)k] ? pl.runs[(size_t)k].bytes : -1;
+      }
+      fold_slices(pl.rounds[q], m, mems, fin, last, landed);
+    }
+    deliver(m, last, pipe.s[q % 3], *pipe.ws[q % 3]);
     ++q;
   }
   for (auto& t : dp.threads) t.join();
@@ -1201,6 +1314,13 @@ void StagedMerge::run_hybrid() {
     lpq_wait();
   }
   const int R = (int)spills_.size();
+  if (direct_ && verify_over_) {  // spills_[r] is the index of group_[r]
+    if (group_.size() != (size_t)R) throw UdaError("direct RPQ: " + std::to_string(R) + " runs indexed of " +
+                                                   std::to_string(group_.size()) + " partitions");
+    for (const Span& sp : group_)
+      slice_sums_.add_run(sp.tail != 0, sp.len, sp.id >= 0 ? map_ids_[(size_t)sp.id] : std::string("?"));
+  }
+  const ChecksumPolicy* const slice_ck = slice_sums_.any() ? &slice_ck_ : nullptr;
   // splitters every ~budget/2 bytes of input (a sample stands for the bytes up to its run's next cut)
   std::vector<int64_t> at((size_t)R, 0), end((size_t)R);
   for (int r = 0; r < R; ++r) end[(size_t)r] = spills_[(size_t)r].bytes;
@@ -1247,8 +1367,10 @@ void StagedMerge::run_hybrid() {
     }
     // views: pinned host spans (spill arena or slice arena): SDMA H2D, not a blit kernel
     return device_merge(*pipe.ws[q % 3], views, Codec::kNone, t_.kind_, kv_, pipe.s[q % 3], nullptr, true,
-                        hybrid_combine_);
+                        hybrid_combine_, 256ll << 20, slice_ck);
   };
+  std::vector<uint8_t*> mems;
+  for (int r = 0; r < R && slice_ck; ++r) mems.push_back(spills_[(size_t)r].mem);
   std::vector<std::future<DeviceMergeOut>> next((size_t)rounds);
   for (int q = 0; q < std::min(rounds, 2); ++q) next[(size_t)q] = std::async(std::launch::async, prep, q);
   for (int q = 0; q < rounds; ++q) {
@@ -1258,6 +1380,7 @@ void StagedMerge::run_hybrid() {
       combine_in_ += m.records_in;
     // workspace (q + 2) % 3 delivered round q - 1 before this iteration
     if (q + 2 < rounds) next[(size_t)q + 2] = std::async(std::launch::async, prep, q + 2);
+    if (slice_ck) fold_slices(slices[(size_t)q], m, mems, end, q + 1 == rounds, nullptr);
     const int64_t td = trace::host_enabled() ? trace::now_ns() : 0;
     deliver(m, q + 1 == rounds, pipe.s[q % 3], *pipe.ws[q % 3]);
     if (td) trace::host_event("rpq_deliver", m.bytes, q, td, trace::now_ns());
@@ -1296,6 +1419,7 @@ void StagedMerge::finish() {
   std::lock_guard<std::mutex> g(t_.st_mu_);
   if (trailers_ > verified_ && verify_ck_.verify && st_.ifile_checksum != "verified")
     st_.ifile_checksum = "skipped-over-budget";  // (host-decoded partitions are verified as they are pulled)
+  st_.gpu_checksum_ms += slice_ms_;  // (rounds after the last run closed)
   if (combine_skipped_) {
     st_.combine = "skipped-over-budget";
   } else if (t_.combine_ != CombineOp::kNone) {

@@ -65,6 +65,8 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
   double round_ms = 0;
   DeviceMergeOut res;
   const bool verify = ck && ck->verify;
+  const bool slice_states = ck && ck->slice_states;
+  if (slice_states && codec != Codec::kNone) throw UdaError("device_merge: slice checksum states of compressed runs");
   auto name_of = [&](const Span& sp) {
     return ck && ck->map_ids && sp.id >= 0 && (size_t)sp.id < ck->map_ids->size() ? (*ck->map_ids)[(size_t)sp.id]
                                                                                    : std::string("?");
@@ -216,7 +218,9 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
     }
     // the partition's bytes as fetched, where they were just staged; the stored value from the host copy
     const int tail = codec != Codec::kNone ? tails[i] : (host_raw.empty() ? in_runs[i].tail : 0);
-    if (tail) {
+    if (slice_states) {  // every run, empty ones too: slice_crc is indexed by run
+      items.push_back(gpu::DeviceChecksum::Item{stage + off, lens[i], std::string(), true, 0});
+    } else if (tail) {
       ++res.trailers;
       const int64_t body = codec != Codec::kNone ? lens[i] - tail : lens[i];
       if (verify)
@@ -228,11 +232,11 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
   if (h2d) gpu::SdmaEngine::wait(ws.h2d_sig);
   if (!items.empty()) {  // behind the copies on s (SDMA copies have landed), ahead of the wait for them
     ws.checksum.reset();
-    ws.checksum.launch(std::move(items), s);
+    ws.checksum.launch(std::move(items), s, slice_states);
   }
   HIP_CHECK(hipStreamSynchronize(s));
   if (ws.checksum.pending()) {
-    ws.checksum.finish(s, true);
+    ws.checksum.finish(s, true, slice_states ? &res.slice_crc : nullptr);
     verified();
   }
   auto t1 = std::chrono::steady_clock::now();

@@ -42,6 +42,8 @@ struct DeviceMergeOut {
   // IFile checksum trailers (uda/ifile.h) found on the merge's runs and stripped; of those, verified
   int64_t trailers = 0, checksum_parts = 0, checksum_bytes = 0;
   double checksum_ms = 0;  // the device CRC, from launch to its result being read
+  // ChecksumPolicy::slice_states: the raw CRC state (gpu::launch_crc32_states) of every input run, in order
+  std::vector<uint32_t> slice_crc;
 };
 
 constexpr int64_t kPieceBytes = 64 << 20;  // D2H piece of the pinned double buffer (hipMemcpy fallback)
@@ -144,6 +146,10 @@ struct Span {
 struct ChecksumPolicy {
   bool verify = true;
   const std::vector<std::string>* map_ids = nullptr;  // for the mismatch message
+  // The runs are slices of partitions (an over-budget RPQ round over uncompressed, unstaged spans): nothing is
+  // verified here; DeviceMergeOut::slice_crc gets every run's raw CRC state, computed where the slices were
+  // just staged, for the caller to fold per partition over its rounds (uda::Crc32Running).
+  bool slice_states = false;
 };
 // Host decode of one compressed partition whose framing the device cannot resolve. *tail = 4 when the
 // blocks end four bytes ahead of the partition's end: those are its IFile checksum and are not decoded.

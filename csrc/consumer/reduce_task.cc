@@ -556,6 +556,10 @@ void ReduceTask::on_init(const InitParams& p_in) {
   const std::string ck = host_->get_conf("mapred.uda.ifile.checksum", "auto");
   if (!checksum_mode_from_conf(ck, &checksum_))
     throw ProtocolError("unknown mapred.uda.ifile.checksum \"" + ck + "\" (auto or off)");
+  // the over-budget GPU hybrid strips them unverified unless told to verify (gpu_merge_staged.cc)
+  const std::string ckob = host_->get_conf("mapred.uda.ifile.checksum.over.budget", "skip");
+  if (!checksum_over_budget_from_conf(ckob, &checksum_over_budget_))
+    throw ProtocolError("unknown mapred.uda.ifile.checksum.over.budget \"" + ckob + "\" (skip or verify)");
   // key-range rounds in which one device merge hands its output over (GenericMerger::merge's round_bytes)
   merge_round_bytes_ = std::max<int64_t>(4 << 10, host_->conf_i64("mapred.uda.gpu.merge.round.bytes", 256ll << 20));
   if (backend_ == "gpu") {

@@ -100,7 +100,8 @@ struct ReduceStats {
   int64_t combine_in_records = 0, combine_groups = 0;
   int64_t merge_rounds = 0;     // GPU: hand-overs of device merges' output (rounds of mapred.uda.gpu.merge.round.bytes)
   // mapred.uda.ifile.checksum (uda/ifile.h): "none" (no partition carried a trailer), "verified", "off"
-  // (trailers stripped, not verified) or "skipped-over-budget" (the GPU hybrid stripped them unverified);
+  // (trailers stripped, not verified) or "skipped-over-budget" (the GPU hybrid stripped them unverified: the
+  // default of mapred.uda.ifile.checksum.over.budget);
   // partitions and body bytes verified; wall time of the device CRC from launch to its result being read
   std::string ifile_checksum = "none";
   int64_t checksum_partitions = 0, checksum_bytes = 0;
@@ -215,6 +216,7 @@ class ReduceTask {
   int delivery_pack_ = 2;                       // mapred.uda.gpu.delivery.pack: colpack version, 0 = off
   CombineOp combine_ = CombineOp::kNone;        // mapred.uda.merge.combine
   ChecksumMode checksum_ = ChecksumMode::kAuto;  // mapred.uda.ifile.checksum
+  bool checksum_over_budget_ = false;            // mapred.uda.ifile.checksum.over.budget = verify (default skip)
   // IFile trailers were detected and stripped: `parts` partitions of `bytes` body bytes verified (by the
   // host as they were pulled, or by the device in `gpu_ms`), or, with parts == 0, left unverified (off)
   void note_checksum(int64_t parts, int64_t bytes, double gpu_ms = 0);

@@ -38,6 +38,16 @@ uint32_t multmodp(uint32_t a, uint32_t b) {
   }
   return p;
 }
+
+// x^(8 * n) by square and multiply over the bits of n, starting from x^8
+uint32_t xpow8(uint64_t n) {
+  uint32_t pw = 0x80000000u, sq = 0x00800000u;  // x^0, x^8
+  for (; n; n >>= 1) {
+    if (n & 1) pw = multmodp(pw, sq);
+    sq = multmodp(sq, sq);
+  }
+  return pw;
+}
 }  // namespace
 
 uint32_t crc32_ieee(const uint8_t* p, size_t n, uint32_t crc) {
@@ -57,13 +67,13 @@ uint32_t crc32_ieee(const uint8_t* p, size_t n, uint32_t crc) {
 
 uint32_t crc32_combine(uint32_t crc_a, uint32_t crc_b, int64_t len_b) {
   if (len_b <= 0) return crc_a ^ crc_b;  // (crc of no bytes is 0)
-  // x^(8 * len_b) by square and multiply over the bits of len_b, starting from x^8
-  uint32_t pw = 0x80000000u, sq = 0x00800000u;  // x^0, x^8
-  for (uint64_t n = (uint64_t)len_b; n; n >>= 1) {
-    if (n & 1) pw = multmodp(pw, sq);
-    sq = multmodp(sq, sq);
-  }
-  return multmodp(pw, crc_a) ^ crc_b;
+  return multmodp(xpow8((uint64_t)len_b), crc_a) ^ crc_b;
+}
+
+// (the map is linear, so it is the same on raw registers as on finalized CRCs: the presets cancel there)
+uint32_t crc32_fold_state(uint32_t state, uint32_t seg_state, int64_t seg_len) {
+  if (seg_len <= 0) return state ^ seg_state;  // (the state of no bytes is 0)
+  return multmodp(xpow8((uint64_t)seg_len), state) ^ seg_state;
 }
 
 int ifile_trailer_bytes(int64_t raw_len, int64_t part_len) {
@@ -90,6 +100,12 @@ bool checksum_mode_from_conf(const std::string& v, ChecksumMode* mode) {
     return true;
   }
   return false;
+}
+
+bool checksum_over_budget_from_conf(const std::string& v, bool* verify) {
+  if (v != "skip" && v != "verify") return false;
+  *verify = v == "verify";
+  return true;
 }
 
 }  // namespace uda

@@ -29,6 +29,13 @@
 // all chunks but the last fold with one constant per lane (x^(8 * 256 KiB * d)) and an xor-reduction,
 // 64 chunks per step; the result is carried over the last chunk's length (square and multiply, once
 // per range) and xored with the last chunk's state.
+//
+// State mode (launch_crc32_states, the kState instantiations): the raw register after a range from a ZERO
+// register, no preset and no final inversion, so a host can chain ranges of one stream:
+// s' = s * x^(8 * len) + state (uda::crc32_fold_state). A range's first chunk then starts from 0 like
+// every other chunk. The virtual zero words in front of a chunk's rows, and the first chunk's missing
+// front in the fold, rest on "zeros ahead of a zero state leave it zero"; that holds for a zero
+// register unchanged (it is where the preset mode's argument starts: its preset enters behind them).
 #include <stdexcept>
 
 #include "crc32_tables.h"
@@ -94,7 +101,8 @@ __device__ __forceinline__ uint32_t crc_step(const uint32_t* tab, uint32_t acc, 
 }
 
 // chunk_crc[c]: the CRC state (not inverted) at the end of chunk c from a zero state at its start, or
-// from the 0xFFFFFFFF preset for a range's first chunk
+// from the 0xFFFFFFFF preset for a range's first chunk (kState: from a zero state there too)
+template <bool kState>
 __global__ void __launch_bounds__(kCrcThreads) crc32_chunks_kernel(const CrcDesc* descs, int n, const int64_t* chunk_first,
                                                                    int64_t total_chunks, uint32_t* chunk_crc) {
   __shared__ uint32_t tab[kTables * 256];
@@ -126,7 +134,7 @@ __global__ void __launch_bounds__(kCrcThreads) crc32_chunks_kernel(const CrcDesc
     if (w0 > e) w0 = e;
     uintptr_t w1 = e & ~(uintptr_t)15;
     if (w1 < w0) w1 = w0;
-    uint32_t st = k == 0 ? 0xFFFFFFFFu : 0u;
+    uint32_t st = !kState && k == 0 ? 0xFFFFFFFFu : 0u;
     for (const uint8_t* q = (const uint8_t*)b; q < (const uint8_t*)w0; ++q) st = crc_byte(tab, st, *q);
     const int64_t nw = (int64_t)((w1 - w0) >> 4);
     if (nw > 0) {
@@ -155,13 +163,15 @@ __global__ void __launch_bounds__(kCrcThreads) crc32_chunks_kernel(const CrcDesc
   }
 }
 
+// out[i]: the CRC of range i; kState: its raw state, not inverted
+template <bool kState>
 __global__ void __launch_bounds__(kLanes) crc32_fold_kernel(const CrcDesc* descs, int n, const int64_t* chunk_first,
                                                             const uint32_t* chunk_crc, uint32_t* out) {
   const int i = blockIdx.x;
   if (i >= n) return;
   const int lane = threadIdx.x;
   const int64_t c0 = chunk_first[i], nc = chunk_first[i + 1] - c0;
-  if (nc <= 0) {  // no bytes: crc32(b"") == 0
+  if (nc <= 0) {  // no bytes: crc32(b"") == 0, and a zero state stays zero
     if (lane == 0) out[i] = 0;
     return;
   }
@@ -180,7 +190,8 @@ __global__ void __launch_bounds__(kLanes) crc32_fold_kernel(const CrcDesc* descs
     const int64_t last_len = (int64_t)((uintptr_t)d.p & 15) + d.len - n1 * kChunkBytes;
     f = gf_mul(f, gf_xpow8((uint64_t)last_len));
   }
-  if (lane == 0) out[i] = ~(f ^ chunk_crc[c0 + nc - 1]);
+  const uint32_t st = f ^ chunk_crc[c0 + nc - 1];
+  if (lane == 0) out[i] = kState ? st : ~st;
 }
 
 __global__ void crc32_trailers_kernel(const CrcDesc* descs, int n, uint32_t* stored) {
@@ -207,18 +218,31 @@ int64_t crc32_chunk_plan(const CrcDesc* descs, int n, int64_t* chunk_first) {
   return total;
 }
 
-void launch_crc32(const CrcDesc* descs, int n, const int64_t* chunk_first, int64_t total_chunks, void* ws,
-                  uint32_t* out, hipStream_t s) {
+namespace {
+template <bool kState>
+void launch_crc32_mode(const CrcDesc* descs, int n, const int64_t* chunk_first, int64_t total_chunks, void* ws,
+                       uint32_t* out, hipStream_t s) {
   if (n <= 0) return;
   if (total_chunks > 0) {
     // enough workgroups to fill the device a few waves deep; a wave strides over the chunks beyond that
     const int64_t want = (total_chunks + kCrcWaves - 1) / kCrcWaves;
     const unsigned blocks = (unsigned)(want < 2048 ? want : 2048);
-    hipLaunchKernelGGL(crc32_chunks_kernel, dim3(blocks), dim3(kCrcThreads), 0, s, descs, n, chunk_first, total_chunks,
-                       static_cast<uint32_t*>(ws));
+    hipLaunchKernelGGL(crc32_chunks_kernel<kState>, dim3(blocks), dim3(kCrcThreads), 0, s, descs, n, chunk_first,
+                       total_chunks, static_cast<uint32_t*>(ws));
   }
-  hipLaunchKernelGGL(crc32_fold_kernel, dim3((unsigned)n), dim3(kLanes), 0, s, descs, n, chunk_first,
+  hipLaunchKernelGGL(crc32_fold_kernel<kState>, dim3((unsigned)n), dim3(kLanes), 0, s, descs, n, chunk_first,
                      static_cast<const uint32_t*>(ws), out);
+}
+}  // namespace
+
+void launch_crc32(const CrcDesc* descs, int n, const int64_t* chunk_first, int64_t total_chunks, void* ws,
+                  uint32_t* out, hipStream_t s) {
+  launch_crc32_mode<false>(descs, n, chunk_first, total_chunks, ws, out, s);
+}
+
+void launch_crc32_states(const CrcDesc* descs, int n, const int64_t* chunk_first, int64_t total_chunks, void* ws,
+                         uint32_t* out, hipStream_t s) {
+  launch_crc32_mode<true>(descs, n, chunk_first, total_chunks, ws, out, s);
 }
 
 void launch_crc32_trailers(const CrcDesc* descs, int n, uint32_t* stored, hipStream_t s) {

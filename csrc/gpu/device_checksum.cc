@@ -9,7 +9,7 @@
 namespace uda {
 namespace gpu {
 
-void DeviceChecksum::launch(std::vector<Item> items, hipStream_t s) {
+void DeviceChecksum::launch(std::vector<Item> items, hipStream_t s, bool states) {
   if (pending_) throw UdaError("DeviceChecksum: a launch is already pending");
   if (items.empty()) return;
   trace::Range tr("uda.ifile_checksum");
@@ -37,24 +37,33 @@ void DeviceChecksum::launch(std::vector<Item> items, hipStream_t s) {
   auto* d_descs = reinterpret_cast<const CrcDesc*>(d);
   auto* d_first = reinterpret_cast<const int64_t*>(d + (size_t)n * sizeof(CrcDesc));
   auto* d_out = reinterpret_cast<uint32_t*>(d + res);
-  launch_crc32(d_descs, n, d_first, chunks, d + ws, d_out, s);
+  if (states) launch_crc32_states(d_descs, n, d_first, chunks, d + ws, d_out, s);
+  else launch_crc32(d_descs, n, d_first, chunks, d + ws, d_out, s);
   bool gather = false;
-  for (const Item& it : items_) gather = gather || !it.stored_known;
+  for (const Item& it : items_) gather = gather || (!states && !it.stored_known);
   if (gather) launch_crc32_trailers(d_descs, n, d_out + n, s);
   HIP_CHECK(hipGetLastError());
   host_.assign((size_t)n * 2, 0);
   HIP_CHECK(hipMemcpyAsync(host_.data(), d_out, (size_t)n * (gather ? 8 : 4), hipMemcpyDeviceToHost, s));
   pending_ = true;
+  states_ = states;
+  if (states) return;
   partitions_ += n;
   bytes_ += bytes;
 }
 
-void DeviceChecksum::finish(hipStream_t s, bool synced) {
+void DeviceChecksum::finish(hipStream_t s, bool synced, std::vector<uint32_t>* states) {
   if (!pending_) return;
   pending_ = false;
   if (!synced) HIP_CHECK(hipStreamSynchronize(s));
   ms_ += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0_).count();
   const size_t n = items_.size();
+  if (states_) {
+    if (!states) throw UdaError("DeviceChecksum: a states launch is finished without a place for them");
+    states->assign(host_.begin(), host_.begin() + (long)n);
+    items_.clear();
+    return;
+  }
   for (size_t i = 0; i < n; ++i) {
     const Item& it = items_[i];
     const uint32_t stored = it.stored_known ? it.stored : host_[n + i];

@@ -26,11 +26,16 @@ class DeviceChecksum {
   };
   // Queues everything on s (descriptor upload, the kernels, the results' download) and returns; nothing
   // is allocated per call once the scratch has grown to the task's shape. One launch may be pending.
-  void launch(std::vector<Item> items, hipStream_t s);
+  // states: the items are consecutive slices of partitions, not partitions (an over-budget RPQ round): the
+  // state kernel runs (launch_crc32_states; body and len alone are read, empty items are fine) and finish()
+  // hands the raw states back for the host to fold (uda::crc32_fold_state). Such a launch counts toward ms()
+  // only: which partitions it completes is the caller's to know.
+  void launch(std::vector<Item> items, hipStream_t s, bool states = false);
   bool pending() const { return pending_; }
   // After s has been synchronized (synced: by the caller, since launch(); else here): throws UdaError
-  // with ifile_checksum_mismatch() of the first partition whose CRC differs from its stored value.
-  void finish(hipStream_t s, bool synced);
+  // with ifile_checksum_mismatch() of the first partition whose CRC differs from its stored value. After a
+  // states launch nothing is compared: *states gets one raw state per item, in the items' order.
+  void finish(hipStream_t s, bool synced, std::vector<uint32_t>* states = nullptr);
   // totals over the launches since reset()
   int64_t partitions() const { return partitions_; }
   int64_t bytes() const { return bytes_; }
@@ -47,7 +52,7 @@ class DeviceChecksum {
   std::vector<Item> items_;
   std::vector<uint8_t> upload_;  // descriptors | chunk_first, kept until the launch has finished
   std::vector<uint32_t> host_;   // computed | stored
-  bool pending_ = false;
+  bool pending_ = false, states_ = false;
   std::chrono::steady_clock::time_point t0_;
   int64_t partitions_ = 0, bytes_ = 0;
   double ms_ = 0;

@@ -364,6 +364,11 @@ size_t crc32_ws_bytes(int64_t total_chunks);
 int64_t crc32_chunk_plan(const CrcDesc* descs, int n, int64_t* chunk_first);
 void launch_crc32(const CrcDesc* descs, int n, const int64_t* chunk_first, int64_t total_chunks, void* ws,
                   uint32_t* out, hipStream_t s);
+// Same contract and chunk plan; out[i] = the raw CRC register after range i from a ZERO register (no
+// 0xFFFFFFFF preset, no final inversion; 0 for an empty range): what uda::crc32_fold_state chains over the
+// consecutive ranges of one stream. In Python terms zlib.crc32(range, 0xFFFFFFFF) ^ 0xFFFFFFFF.
+void launch_crc32_states(const CrcDesc* descs, int n, const int64_t* chunk_first, int64_t total_chunks, void* ws,
+                         uint32_t* out, hipStream_t s);
 // stored[i] = the big-endian int in the four bytes after range i (its IFile trailer)
 void launch_crc32_trailers(const CrcDesc* descs, int n, uint32_t* stored, hipStream_t s);
 

@@ -199,6 +199,29 @@ uint32_t crc32_ieee(const uint8_t* p, size_t n, uint32_t crc = 0);
 // zlib's crc32_combine(): the CRC of A || B from crc(A), crc(B) and len(B), i.e. crc_a times
 // x^(8 * len_b) modulo the polynomial, plus crc_b.
 uint32_t crc32_combine(uint32_t crc_a, uint32_t crc_b, int64_t len_b);
+// The same step on raw CRC registers (no preset, no final inversion): `state` carried over a following
+// segment of seg_len bytes whose own register from zero is seg_state (gpu::launch_crc32_states), i.e.
+// state * x^(8 * seg_len) + seg_state. Square and multiply: 32 multiplies at most per call.
+uint32_t crc32_fold_state(uint32_t state, uint32_t seg_state, int64_t seg_len);
+// The CRC32 of a stream that arrives as consecutive segments, some as device-computed states and some as
+// host bytes: the over-budget GPU merge's view of a partition (mapred.uda.ifile.checksum.over.budget).
+class Crc32Running {
+ public:
+  void append_state(uint32_t seg_state, int64_t len) {
+    state_ = crc32_fold_state(state_, seg_state, len);
+    bytes_ += len;
+  }
+  void append_bytes(const uint8_t* p, size_t n) {  // bytewise on the host: for the bytes no device segment carries
+    state_ = ~crc32_ieee(p, n, ~state_);
+    bytes_ += (int64_t)n;
+  }
+  uint32_t value() const { return ~state_; }  // zlib's crc32() of everything appended
+  int64_t bytes() const { return bytes_; }
+
+ private:
+  uint32_t state_ = 0xFFFFFFFFu;
+  int64_t bytes_ = 0;
+};
 // Trailer bytes (0 or kIFileChecksumBytes) of an UNCOMPRESSED partition from the lengths its index
 // gives: part_len == raw_len + 4 has one; part_len == raw_len, a raw_len <= 0 (an answer that does not
 // say) and anything else have none. A compressed partition's lengths cannot tell: the framing walk
@@ -212,5 +235,10 @@ std::string ifile_checksum_mismatch(const std::string& map_id, uint32_t stored, 
 // not verified). false for any other value.
 enum class ChecksumMode { kAuto, kOff };
 bool checksum_mode_from_conf(const std::string& v, ChecksumMode* mode);
+// mapred.uda.ifile.checksum.over.budget: what the over-budget GPU hybrid merge does with the trailers under
+// "auto": "skip" (the default: stripped unverified, ifile_checksum "skipped-over-budget") or "verify" (LPQ
+// groups on the device as any merge; direct RPQ rounds fold per-slice device states per partition).
+// *verify says which; false for any other value.
+bool checksum_over_budget_from_conf(const std::string& v, bool* verify);
 
 }  // namespace uda

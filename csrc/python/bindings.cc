@@ -862,6 +862,9 @@ PYBIND11_MODULE(_uda_native, m) {
   }, py::arg("data"), py::arg("seed") = 0);
   m.def("crc32_combine", [](uint32_t a, uint32_t b, int64_t len_b) { return crc32_combine(a, b, len_b); },
         py::arg("crc_a"), py::arg("crc_b"), py::arg("len_b"));
+  m.def("crc32_fold_state", [](uint32_t state, uint32_t seg_state, int64_t seg_len) {
+    return crc32_fold_state(state, seg_state, seg_len);
+  }, py::arg("state"), py::arg("seg_state"), py::arg("seg_len"));
   m.def("ifile_trailer_bytes", &ifile_trailer_bytes, py::arg("raw_len"), py::arg("part_len"));
   // the trailer-aware host framing walk of one block-compressed stream: (blocks, tail bytes)
   m.def("plan_block_streams", [](int codec, py::bytes b) {
@@ -987,7 +990,8 @@ PYBIND11_MODULE(_uda_native, m) {
   m.def("gpu_crc32_chunk_bytes", [] { return gpu::crc32_chunk_bytes(); });
   // zlib.crc32 of every input by one launch of the device kernels (crc32.hip): the inputs lie in one device
   // buffer, each at an address that is `misalign` modulo 16
-  m.def("gpu_crc32", [](const std::vector<std::string>& inputs, int misalign, int device) {
+  // (states: launch_crc32_states, the raw register after every input from a zero register)
+  auto gpu_crc32 = [](const std::vector<std::string>& inputs, int misalign, int device, bool states) {
     if (misalign < 0 || misalign > 15) throw py::value_error("misalign must be 0..15");
     const int n = (int)inputs.size();
     std::vector<uint32_t> out((size_t)n, 0);
@@ -1017,12 +1021,20 @@ PYBIND11_MODULE(_uda_native, m) {
         ws(gpu::crc32_ws_bytes(chunks));
     HIP_CHECK(hipMemcpyAsync(d_descs.as(), descs.data(), (size_t)n * sizeof(gpu::CrcDesc), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(d_first.as(), first.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
-    gpu::launch_crc32(d_descs.as<gpu::CrcDesc>(), n, d_first.as<int64_t>(), chunks, ws.as(), d_out.as<uint32_t>(), s);
+    (states ? gpu::launch_crc32_states : gpu::launch_crc32)(d_descs.as<gpu::CrcDesc>(), n, d_first.as<int64_t>(), chunks,
+                                                            ws.as(), d_out.as<uint32_t>(), s);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(out.data(), d_out.as(), (size_t)n * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     HIP_CHECK(hipStreamDestroy(s));
     return out;
+  };
+  m.def("gpu_crc32", [gpu_crc32](const std::vector<std::string>& inputs, int misalign, int device) {
+    return gpu_crc32(inputs, misalign, device, false);
+  }, py::arg("inputs"), py::arg("misalign") = 0, py::arg("device") = 0);
+  // zlib.crc32(input, 0xFFFFFFFF) ^ 0xFFFFFFFF of every input: what crc32_fold_state chains
+  m.def("gpu_crc32_states", [gpu_crc32](const std::vector<std::string>& inputs, int misalign, int device) {
+    return gpu_crc32(inputs, misalign, device, true);
   }, py::arg("inputs"), py::arg("misalign") = 0, py::arg("device") = 0);
   // benchmarks/run_configs.py checksum: `parts` ranges of `part_bytes` random bytes; per repetition the
   // milliseconds (hipEvents) of the CRC launch and of launch_batched_copy of the same bytes
