@@ -44,6 +44,7 @@
 #include "kernels.h"
 #include "disk_store.h"
 #include "sdma.h"
+#include "shuffle_plan.h"
 
 namespace uda {
 namespace gpu {
@@ -367,7 +368,7 @@ class ShuffleJob {
   std::vector<uint64_t> local_dest_checksums() const { return dest_checksum_; }
   std::vector<int64_t> local_dest_records() const { return dest_records_; }
   // Records each of this GPU's reducers receives per step (after plan()).
-  std::vector<int64_t> reducer_records() const { return reducer_records_; }
+  std::vector<int64_t> reducer_records() const { return plan_.reducer_records; }
   int64_t store_bytes() const { return store_bytes_; }
   double map_sort_ms() const { return map_sort_ms_; }  // cfg.map_sort: device time of the map-side sorts
   // Device address / size of MOF m in the partition store (host address for the host tier).
@@ -379,13 +380,13 @@ class ShuffleJob {
     store_base_ = store_dev_base_ = nullptr;
   }
   int64_t mof_bytes(int m) const { return mof_off_.at(m + 1) - mof_off_.at(m); }
-  int64_t max_round_records() const { return max_round_records_; }
+  int64_t max_round_records() const { return plan_.max_round_records; }
   // bytes this rank sends to each peer per step (self: 0)
   std::vector<int64_t> peer_send_bytes() const {
     std::vector<int64_t> v((size_t)cfg_.world, 0);
-    for (const auto& rp : plans_)
+    for (const auto& rp : plan_.rounds)
       for (int p = 0; p < (int)rp.send.size() && p < cfg_.world; ++p)
-        for (const auto& sp : rp.send[p]) v[(size_t)p] += sp.bytes;
+        for (const auto& sl : rp.send[p]) v[(size_t)p] += sl.bytes;
     return v;
   }
   int comm_ranks() const { return exchange_ ? exchange_->comm_ranks() : 1; }
@@ -398,22 +399,39 @@ class ShuffleJob {
   std::vector<uint8_t> read_partition(int m, int d) const;
 
  private:
-  struct RoundPlan {
-    // send[p]: slices to GPU p, order (reducer i, local map m); empty for p == me
-    std::vector<std::vector<Span>> send;
-    int64_t send_bytes = 0;
-    // recv_cnt[(s*R + i)*M + j]: records of source s's map j for my reducer i
-    std::vector<int64_t> recv_cnt;
-    std::vector<int64_t> recv_off;     // byte offset of that slice in the receive slot (s-major)
-    std::vector<int64_t> self_beg;     // [i*M + m] first record of my own cell (i, q) in run (m, me)
-    std::vector<int64_t> group_recs;   // records per reducer this round
-    int64_t recv_records = 0;
-    // spill tiers, world > 1: the outgoing slices are staged into HBM, one contiguous region per
-    // peer (send staging of parity q & 1), and travel as one message per peer; the receive side
-    // takes them as one span per source (its slices from a source are contiguous in the slot)
-    std::vector<std::vector<Span>> staged_send, staged_recv;
+  // One run_step(): its locals and one method per thing the round loop does (shuffle_step.cc).
+  class Step;
+  // Counters of one step, all under mu_: written by the delivery threads, read out when the step ends.
+  struct StepCounters {
+    int eof_count = 0;          // reducers whose last buffer went out
+    int64_t buffers = 0;
+    int error = 0;              // first nonzero sink return
+    double d2h_ms = 0;
+    int64_t d2h_bytes = 0, packed = 0, raw = 0, delta = 0;
+    int64_t stride_min = -1, stride_max = 0;
+    double unpack_ms = 0;
+    // link occupancy (StepStats lead_in_ms ...). A piece is in flight from its issue until someone sees its
+    // signal or event complete.
+    double t0_ms = 0, first_issue_ms = -1, last_landing_ms = -1, idle_since_ms = -1, eof_done_ms = -1;
+    double link_idle_ms = 0, slot_wait_ms = 0;
+    bool check_delivery = false;  // this step checksums what the D2H reads and what the consumers receive
+  };
+  // A round's exchange arguments: spans per peer. HBM store: the outgoing slices in the store and the
+  // receive slot's slices; spill tiers: one span of the send staging per peer, one of the slot per source.
+  struct RoundSpans {
+    std::vector<std::vector<Span>> send, recv;
   };
   void compute_plans();
+  // compute_plans(), part by part: the cell splits of the local runs, the checksum of every (run, cell)
+  // slice, the round buffers, the delivery-pack tables and the per-round descriptor tables
+  std::vector<int64_t> split_runs();
+  std::vector<int64_t> checksum_cells();
+  void alloc_store();
+  void alloc_round_buffers();
+  void plan_delivery_pack();
+  void build_round_spans();
+  void upload_check_tables();
+  void upload_h2d_tables();
   void copy_loop();
   void consume_loop(int reducer);
   void wait_exchange_ok();
@@ -431,6 +449,7 @@ class ShuffleJob {
 
   ShuffleConfig cfg_;
   int R_ = 1, Q_ = 1, C_ = 1;  // reducers, rounds, cells (R*Q) per GPU
+  ShuffleGeometry geo_;        // the same with world, maps and rank: the plan tables' index functions
   std::unique_ptr<Exchange> exchange_;
   std::unique_ptr<DiskStore> disk_;
   hipStream_t s_comm_ = nullptr, s_compute_ = nullptr, s_copy_ = nullptr;
@@ -445,12 +464,11 @@ class ShuffleJob {
   std::vector<uint64_t> dest_checksum_;
   std::vector<uint64_t> run_gen_ck_;  // per run: the checksum its generation kernel computed
   std::vector<int64_t> dest_records_;
-  std::vector<int64_t> reducer_records_;
   std::vector<uint64_t> bounds_;  // W x (C-1) x 2
   DeviceBuffer d_bounds_, d_run_bases_, d_run_nrec_, d_bound_set_, d_split_out_;
   std::vector<int64_t> split_pos_;  // [run r][cell c .. C]: (C+1) record positions per run
-  std::vector<RoundPlan> plans_;
-  int64_t max_round_records_ = 0;
+  ShufflePlan plan_;               // shuffle_plan.h: every round as offsets
+  std::vector<RoundSpans> xchg_;   // per round
   std::vector<DeviceBuffer> recv_slots_, out_slots_;
   // spill tiers, world > 1: outgoing slices of round q staged in send_staging_[q & 1] (per peer
   // contiguous); sent_ev_[q & 1] marks the exchange that reads them on the comm stream
@@ -462,29 +480,21 @@ class ShuffleJob {
   // exchange verification (validate steps, world > 1): per round, the received peer slices and
   // the checksums their senders computed at plan()
   std::vector<DeviceBuffer> d_verify_runs_, d_verify_expect_;
-  std::vector<int> verify_n_;
-  std::vector<int64_t> verify_max_nrec_;
   DeviceBuffer d_verify_got_;
   // validate steps, per round: the own cells the merge reads (in place, or staged into the receive slot)
-  // with their plan-time checksums, the expected checksum of every (round, reducer) output (the sum of
-  // its input slices' plan-time checksums), and the device-side per-round results:
+  // with their plan-time checksums (the expected checksum of every (round, reducer) output, the sum of its
+  // input slices' plan-time checksums, is plan_.expect_group_ck), and the device-side per-round results:
   //   diag[q * diag_stride() + {0,1,2,3}] = peer-slice mismatches before / after the merge, own-cell
   //   mismatches before / after; + 4 + i: the checksum of reducer i's merged output
   std::vector<DeviceBuffer> d_own_runs_, d_own_expect_;
-  std::vector<int> own_n_;
-  std::vector<int64_t> own_max_nrec_;
-  std::vector<uint64_t> expect_group_ck_;  // [q * R + i]
   DeviceBuffer d_diag_;
   int diag_stride() const { return 4 + R_; }
   // check_delivery: per (round, reducer) checksum of the output slot right before its D2H (copy thread)
   // and of the bytes the consumer threads received
   std::vector<uint64_t> pre_d2h_ck_, delivered_ck_;
-  bool step_check_delivery_ = false;
   DeviceBuffer d_d2h_runs_, d_d2h_ck_;
-  // pinned-DRAM tier: per-round batched H2D copy descriptors (device), their count and largest size
+  // pinned-DRAM tier: per-round batched H2D copy descriptors (device), plan_.rounds[q].h2d with addresses
   std::vector<DeviceBuffer> h2d_descs_;
-  std::vector<int> h2d_n_;
-  std::vector<int64_t> h2d_max_;
   int h2d_blocks_ = 2048;  // workgroups per descriptor (UDA_H2D_BLOCKS)
   bool sdma_h2d_ = true;   // pinned-DRAM tier, W == 1: stage on an SDMA engine (UDA_H2D_SDMA)
   hipStream_t s_stage_ = nullptr;  // disk tier, W == 1: H2D of the staging thread
@@ -549,20 +559,11 @@ class ShuffleJob {
   std::thread copy_thr_;
   std::vector<std::thread> consumers_;
   bool stop_ = false;
-  int eof_count_ = 0;
-  int64_t step_buffers_ = 0;
-  int step_error_ = 0;
+  StepCounters step_;
   std::string step_error_msg_;
-  double step_d2h_ms_ = 0;
-  int64_t step_d2h_bytes_ = 0, step_packed_ = 0, step_raw_ = 0, step_delta_ = 0;
-  int64_t step_stride_min_ = -1, step_stride_max_ = 0;
-  double step_unpack_ms_ = 0;
-  // link occupancy (StepStats lead_in_ms ...), all under mu_. A piece is in flight from its issue until
-  // someone sees its signal or event complete; slot_flying_[k]: ring slot k holds such a piece.
+  // slot_flying_[k]: ring slot k holds a piece in flight (StepCounters' link occupancy), under mu_
   std::vector<bool> slot_flying_;
   int flying_ = 0;
-  double step_t0_ms_ = 0, first_issue_ms_ = -1, last_landing_ms_ = -1, idle_since_ms_ = -1, eof_done_ms_ = -1;
-  double step_link_idle_ms_ = 0, step_slot_wait_ms_ = 0;
   void note_issue(int k, double now);      // mu_ held
   void note_landing(int k, double now);    // mu_ held
   void poll_landings();                    // mu_ held: pieces whose copy is done but nobody has waited for yet

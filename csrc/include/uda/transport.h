@@ -10,7 +10,7 @@
 // Backends here: `loopback` (in-process, zero-copy into the client buffer: the RDMA-WRITE
 // analogue) and `tcp` (sockets, the same RTS/ACK strings inside a 16-byte netlev header, for
 // multi-process / multi-host runs). The GPU data plane does not use this interface: partitions
-// move HBM->HBM through RCCL all-to-all rounds (csrc/gpu/device_engine.cc).
+// move HBM->HBM through RCCL all-to-all rounds (csrc/gpu/shuffle_step.cc).
 #pragma once
 #include <cstdint>
 #include <functional>
