@@ -26,9 +26,13 @@
 namespace uda {
 namespace gpu {
 
+constexpr int kSampleKey = 64;  // content bytes kept per sampled key (a bound may be any byte string)
+constexpr int kSamplesPerRound = 512;
+
 struct GenericRoundsPlan {
   int rounds = 1;
   std::vector<int64_t> pos;  // [run][round 0..Q]: byte offsets (pos(k, Q) = run bytes)
+  std::vector<std::string> bounds;  // the rounds - 1 bound strings the runs were split by, ascending
   int64_t max_round_bytes = 0;
   double plan_ms = 0;
   int64_t at(int k, int q) const { return pos[(size_t)k * (rounds + 1) + q]; }
@@ -40,6 +44,8 @@ struct GenericRoundsWs {
 };
 
 // Plan Q = ceil(total / round_bytes) rounds (fewer if the keys do not allow more distinct bounds).
+// Round 0 is the small one (what Q - 1 whole rounds leave over, at least an eighth of an even share): its
+// merge is the only one that no delivery overlaps. The others share the rest evenly.
 // runs: device pointers to IFile streams (records, optionally followed by the EOF marker).
 // Synchronizes `s`.
 GenericRoundsPlan plan_generic_rounds(const std::vector<const uint8_t*>& runs, const std::vector<int64_t>& run_bytes,

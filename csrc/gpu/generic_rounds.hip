@@ -16,9 +16,6 @@ namespace uda {
 namespace gpu {
 
 namespace {
-constexpr int kSampleKey = 64;      // content bytes kept per sampled key (a bound may be any byte string)
-constexpr int kSamplesPerRound = 512;
-
 // Key content of the record at p (n bytes of stream left): pointer and length. Numeric kinds: the content
 // is the key's sortable word, big-endian in the caller's `norm` (the bytes F2 will compare; a key of the
 // wrong length is the word 0 here and fails the task in F2 of its round).
@@ -322,13 +319,17 @@ GenericRoundsPlan plan_generic_rounds(const std::vector<const uint8_t*>& runs, c
   for (int64_t i = 0; i < ns; ++i)
     if (kl[(size_t)i] >= 0) sk.emplace_back(reinterpret_cast<const char*>(&keys[(size_t)i * kSampleKey]), (size_t)kl[(size_t)i]);
   std::sort(sk.begin(), sk.end());  // unsigned bytewise, a prefix first: the key order on content
-  // round 0 takes an eighth of a round's share: its merge is the only one not overlapped with a
-  // delivery, so the consumer starts early; rounds 1..want split the rest evenly
+  // `want` rounds, none above round_bytes, the first one as small as that allows: round 0 takes what
+  // want - 1 whole rounds leave over, and at least an eighth of an even share (its merge is the only
+  // one not overlapped with a delivery, so the consumer starts early); rounds 1..want-1 split the rest
+  // evenly. (An eighth of a share in front of `want` even rounds was one round more than promised.)
   std::vector<std::string> bounds;
   std::vector<double> cut;
-  const double first = 1.0 / (8.0 * want);
+  const int64_t rb = std::max<int64_t>(round_bytes, 1);
+  const double left_over = (double)(total - (int64_t)(want - 1) * rb) / (double)total;  // in (0, 1 / (want - 1))
+  const double first = std::max(left_over, 1.0 / (8.0 * want));
   cut.push_back(first);
-  for (int q = 1; q < want; ++q) cut.push_back(first + (1.0 - first) * q / want);
+  for (int q = 1; q + 1 < want; ++q) cut.push_back(first + (1.0 - first) * q / (want - 1));
   for (double f : cut) {
     if (sk.empty()) break;
     const std::string& b = sk[(size_t)std::min<int64_t>((int64_t)sk.size() - 1, (int64_t)(f * (double)sk.size()))];
@@ -368,6 +369,7 @@ GenericRoundsPlan plan_generic_rounds(const std::vector<const uint8_t*>& runs, c
     for (int k = 0; k < K; ++k) b += plan.at(k, q + 1) - plan.at(k, q);
     plan.max_round_bytes = std::max(plan.max_round_bytes, b);
   }
+  plan.bounds = std::move(bounds);
   plan.plan_ms = now_ms() - t0;
   return plan;
 }

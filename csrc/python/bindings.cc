@@ -29,6 +29,7 @@
 #include "exchange.h"
 #include "api_bench.h"
 #include "generic_merger.h"
+#include "generic_rounds.h"
 #include "j2c_sink.h"
 #include "stream_sampler.h"
 #include "uda/aio.h"
@@ -1941,6 +1942,91 @@ PYBIND11_MODULE(_uda_native, m) {
     d["len_cap"] = gpu::generic_len_cap();
     return d;
   });
+  // The constants of the key-range round planner (generic_rounds.h). Callable without a device.
+  m.def("gpu_rounds_geometry", [] {
+    py::dict d;
+    d["sample_key"] = gpu::kSampleKey;
+    d["samples_per_round"] = gpu::kSamplesPerRound;
+    return d;
+  });
+  // The two planners of generic_rounds.h on their own (tests). Every run lies in a device allocation of its
+  // own and starts `misalign` bytes past that allocation's 256-byte-aligned base: partitions sit at any
+  // offset of a MOF, progressive windows start at any byte.
+  struct RoundRuns {
+    std::vector<gpu::DeviceBuffer> bufs;
+    std::vector<const uint8_t*> ptrs;
+    std::vector<int64_t> bytes;
+    hipStream_t s = nullptr;
+    ~RoundRuns() {
+      if (s) (void)hipStreamDestroy(s);
+    }
+    void upload(const std::vector<std::string>& runs, int misalign, int device) {
+      if (misalign < 0 || misalign > 255) throw py::value_error("misalign must be 0..255");
+      HIP_CHECK(hipSetDevice(device));
+      HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      bufs.resize(runs.size());
+      for (size_t i = 0; i < runs.size(); ++i) {
+        bufs[i].alloc_local(runs[i].size() + (size_t)misalign + 256);
+        uint8_t* base = bufs[i].as<uint8_t>();
+        if ((uintptr_t)base & 255) throw UdaError("device allocation is not 256-byte aligned");
+        if (!runs[i].empty())
+          HIP_CHECK(hipMemcpyAsync(base + misalign, runs[i].data(), runs[i].size(), hipMemcpyHostToDevice, s));
+        ptrs.push_back(base + misalign);
+        bytes.push_back((int64_t)runs[i].size());
+      }
+      HIP_CHECK(hipStreamSynchronize(s));
+    }
+  };
+  // plan_generic_rounds over whole runs: {"rounds", "pos": [run][0..rounds], "bounds", "max_round_bytes"}
+  m.def("gpu_plan_generic_rounds", [](const std::vector<std::string>& streams, int kind, int64_t round_bytes,
+                                      int misalign, int device) {
+    gpu::GenericRoundsPlan plan;
+    {
+      py::gil_scoped_release rel;
+      RoundRuns rr;
+      rr.upload(streams, misalign, device);
+      gpu::GenericRoundsWs ws;
+      plan = gpu::plan_generic_rounds(rr.ptrs, rr.bytes, kind, round_bytes, ws, rr.s);
+    }
+    py::list pos, bounds;
+    for (size_t k = 0; k < streams.size(); ++k) {
+      py::list row;
+      for (int q = 0; q <= plan.rounds; ++q) row.append(plan.at((int)k, q));
+      pos.append(row);
+    }
+    for (const std::string& b : plan.bounds) bounds.append(py::bytes(b));
+    py::dict d;
+    d["rounds"] = plan.rounds;
+    d["pos"] = pos;
+    d["bounds"] = bounds;
+    d["max_round_bytes"] = plan.max_round_bytes;
+    return d;
+  }, py::arg("streams"), py::arg("kind"), py::arg("round_bytes"), py::arg("misalign") = 0, py::arg("device") = 0);
+  // plan_progressive_split: windows[k] is uploaded whole, its first avail[k] bytes count as landed.
+  // {"complete", "split", "bounded", "bound"}
+  m.def("gpu_plan_progressive_split", [](const std::vector<std::string>& windows, const std::vector<int64_t>& avail,
+                                         const std::vector<bool>& final_run, int kind, int misalign, int device) {
+    if (avail.size() != windows.size() || final_run.size() != windows.size())
+      throw py::value_error("windows, avail and final differ in length");
+    for (size_t k = 0; k < windows.size(); ++k)
+      if (avail[k] < 0 || avail[k] > (int64_t)windows[k].size()) throw py::value_error("avail outside its window");
+    gpu::ProgressiveSplit ps;
+    {
+      py::gil_scoped_release rel;
+      RoundRuns rr;
+      rr.upload(windows, misalign, device);
+      gpu::GenericRoundsWs ws;
+      const std::vector<char> fin(final_run.begin(), final_run.end());
+      ps = gpu::plan_progressive_split(rr.ptrs, avail, fin, kind, ws, rr.s);
+    }
+    py::dict d;
+    d["complete"] = ps.complete;
+    d["split"] = ps.split;
+    d["bounded"] = ps.bounded;
+    d["bound"] = py::bytes(ps.bound);
+    return d;
+  }, py::arg("windows"), py::arg("avail"), py::arg("final"), py::arg("kind"), py::arg("misalign") = 0,
+        py::arg("device") = 0);
   // Merge IFile runs (any bytes-like objects, read in place) on the device. Returns
   // (merged bytes, buffer cuts, records, merge passes, device merge ms, runs indexed serially, records merged).
   // combine: "none" or an op of uda/combine.h (sum.int, sum.long, min.int, max.int, min.long, max.long,

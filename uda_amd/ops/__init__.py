@@ -61,6 +61,36 @@ def merge_runs_streamed(runs: list[bytes], key_class: str, kv_buf: int = 1 << 20
     return merged, cuts, dict(records=records, records_in=records_in, rounds=rounds, held_records=held)
 
 
+def _key_kind(n, key_class: str, key_order: str) -> int:
+    kind = n.key_kind_ordered(key_class, key_order)
+    if kind < 0:
+        raise ValueError(f"unsupported key class {key_class!r} under key_order={key_order!r}")
+    return kind
+
+
+def plan_generic_rounds(runs: list[bytes], key_class: str, round_bytes: int, key_order: str = "reference",
+                        misalign: int = 0, gpu_index: int = 0) -> dict:
+    """The key-range round plan of the device-generic merge (csrc/gpu/generic_rounds.h) for whole runs:
+    rounds, pos[run][0..rounds] (byte offsets), bounds (the rounds - 1 strings the runs were split by) and
+    max_round_bytes. Every run starts `misalign` bytes past a 256-byte-aligned device address."""
+    n = native()
+    if n.device_count() <= 0:
+        raise RuntimeError("plan_generic_rounds: no HIP device visible")
+    return n.gpu_plan_generic_rounds(list(runs), _key_kind(n, key_class, key_order), round_bytes, misalign, gpu_index)
+
+
+def plan_progressive_split(windows: list[bytes], avail: list[int], final: list[bool], key_class: str,
+                           key_order: str = "reference", misalign: int = 0, gpu_index: int = 0) -> dict:
+    """The split of a progressive merge phase: windows[k] are the bytes of run k not merged yet, the first
+    avail[k] of them landed; final[k]: the window reaches the run's end. Returns complete (end of the last
+    whole landed record), split (the bytes of each window safe to merge now), bounded and bound."""
+    n = native()
+    if n.device_count() <= 0:
+        raise RuntimeError("plan_progressive_split: no HIP device visible")
+    return n.gpu_plan_progressive_split(list(windows), list(avail), [bool(f) for f in final],
+                                        _key_kind(n, key_class, key_order), misalign, gpu_index)
+
+
 def buffers(merged: bytes, cuts: list[int]) -> list[bytes]:
     """Split a merged stream at the cut offsets into delivery buffers, EOF in the last one."""
     out = [merged[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
