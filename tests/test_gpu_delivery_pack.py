@@ -25,12 +25,12 @@ class Collector:
         self.lens[r].append(len(b))
 
 
-def _run(delivery_pack, d2h, validate=False, **kw):
+def _run(delivery_pack, d2h, validate=False, bounds_fn=None, **kw):
     from uda_amd.models.terasort import TeraSortConfig, TeraSortShuffle
     cfg = TeraSortConfig(**{**SHAPE, **kw}, delivery_pack=delivery_pack, d2h=d2h, validate=validate,
                          check_delivery=validate)
     j = TeraSortShuffle(DistContext(), cfg, device=0)
-    j.setup()
+    j.setup(bounds_fn=bounds_fn)
     sink = Collector(cfg.reducers)
     j.use_python_sink(sink, with_reducer=True)
     st = j.step(validate=validate)
@@ -79,21 +79,19 @@ def test_environment_switch_forces_pack_off(require_gpu, monkeypatch):
     assert st["packed_pieces"] == 0 and "pack=off" in j.job.delivery_name
 
 
-def test_reducer_without_records_in_a_round_gets_one_eof(require_gpu, monkeypatch):
+def test_reducer_without_records_in_a_round_gets_one_eof(require_gpu):
     """Cells (reducer 0, round 0), (reducer 1, round 1) and (reducer 2, round 1) are empty: an empty
     first round, an empty final round after data, and a final round whose EOF travels alone."""
-    import uda_amd.models.terasort as ts
-    orig = ts.round_bounds
+    from uda_amd.parallel.plan import round_bounds
 
     def bounds_with_empty_cells(per_dest, cells):
-        b = orig(per_dest, cells).copy()  # (1, 5, 2): cell c = [bound c-1, bound c), c = reducer * 2 + round
+        b = round_bounds(per_dest, cells).copy()  # (1, 5, 2): cell c = [bound c-1, bound c), c = reducer * 2 + round
         b[0, 0] = 0
         b[0, 3] = b[0, 2]
         b[0, 4] = (np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64(0xFFFF) << np.uint64(48))
         return b
 
-    monkeypatch.setattr(ts, "round_bounds", bounds_with_empty_cells)
-    j, st, sink = _run("auto", "sdma", validate=True, rows_per_gpu=60_000)
+    j, st, sink = _run("auto", "sdma", validate=True, bounds_fn=bounds_with_empty_cells, rows_per_gpu=60_000)
     from uda_amd.utils.ifile import J2CQueueReader
     recs = list(j.job.reducer_records())
     assert all(n > 0 for n in recs)

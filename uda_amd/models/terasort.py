@@ -85,7 +85,10 @@ class TeraSortShuffle:
         self.expected_records = None
         self.setup_s = {}
 
-    def setup(self) -> None:
+    def setup(self, bounds_fn=None) -> None:
+        """bounds_fn(per_dest_samples, cells) -> (world, cells-1, 2) uint64 ascending bounds per destination;
+        the default is round_bounds (quantiles of the key sample). Called after generate(), so a builder may
+        read the store's keys (job.read_partition); every rank must pass the same function."""
         n = native()
         t0 = time.perf_counter()
         if self.ctx.world > 1:
@@ -119,8 +122,8 @@ class TeraSortShuffle:
         for d in range(self.ctx.world):
             parts = [g[d] for g in gathered if g[d].size]
             per_dest.append(np.concatenate(parts) if parts else np.zeros((0, 2), np.uint64))
-        bounds = round_bounds(per_dest, self.cfg.rounds * self.cfg.reducers)
-        self.job.set_bounds(np.ascontiguousarray(bounds.reshape(-1)))
+        bounds = (bounds_fn or round_bounds)(per_dest, self.cfg.rounds * self.cfg.reducers)
+        self.job.set_bounds(np.ascontiguousarray(np.asarray(bounds, np.uint64).reshape(-1)))
         self.job.plan()
         t3 = time.perf_counter()
         # expected per-reducer checksum/records for validation
@@ -241,10 +244,12 @@ def check_stats(stats: dict, expected_records: int, expected_checksum: int, redu
             raise AssertionError("checksum mismatch " + stats.get("diag", ""))
 
 
-def make_local_group(world: int, cfg: TeraSortConfig, device: int = 0, group: str = "local"):
+def make_local_group(world: int, cfg: TeraSortConfig, device: int = 0, group: str = "local", bounds_fn=None):
     """Single-process rehearsal of a `world`-rank shuffle: every rank is a ShuffleJob on `device`
     driven from its own thread, exchanging rounds through device memcpys with the same pack /
-    all-to-all-v schedule as the RCCL path. Returns (jobs, expected_checksums, expected_records)."""
+    all-to-all-v schedule as the RCCL path. Returns (jobs, expected_checksums, expected_records).
+    bounds_fn(per_dest_samples, cells) replaces round_bounds (TeraSortShuffle.setup); it is called once,
+    after every rank's generate(), and may read the jobs' stores."""
 
     n = native()
     records_per_map = max(1, cfg.rows_per_gpu // cfg.maps_per_rank)
@@ -265,7 +270,8 @@ def make_local_group(world: int, cfg: TeraSortConfig, device: int = 0, group: st
     for d in range(world):
         parts = [np.asarray(s[d]) for s in local if np.asarray(s[d]).size]
         per_dest.append(np.concatenate(parts) if parts else np.zeros((0, 2), np.uint64))
-    bounds = np.ascontiguousarray(round_bounds(per_dest, cfg.rounds * cfg.reducers).reshape(-1))
+    bounds = (bounds_fn or round_bounds)(per_dest, cfg.rounds * cfg.reducers)
+    bounds = np.ascontiguousarray(np.asarray(bounds, np.uint64).reshape(-1))
     for j in jobs:
         j.set_bounds(bounds)
     run_collective(jobs, lambda j: j.plan())
