@@ -8,7 +8,8 @@
                       write_kv_to_stream packing) on TeraSort runs on this host's CPU.
   secondary_sort      variable-length Text keys with long common prefixes + partition skew: GPU generic
                       merge (F1/F2/F3/F4 kernels) vs the CPU heap merge on the same runs.
-  decode              F6 Snappy / LZO1X block decode on the device vs the host decoder.
+  decode              F6 Snappy / LZO1X block decode on the device vs the host decoder; --codec zlib: the
+                      device inflate (one wave per stream, --maps streams) vs the system zlib.
   netmerger           secondary-sort data through provider -> NetMerger -> dataFromUda: CPU heap merge vs
                       GPU backend (online and hybrid LPQ/RPQ).
   aio                 AsyncIO (io_uring / thread pool, O_DIRECT) read bandwidth vs sequential pread.
@@ -187,6 +188,8 @@ def decode(args) -> dict:
     """F6: device block decode of block-compressed IFile runs (secondary-sort data) vs host decode."""
     from uda_amd import native
     n = native()
+    if args.codec == "zlib":
+        return decode_zlib(args, n)
     codec = {"snappy": 1, "lzo": 2, "lz4": 3}[args.codec]
     rows = int(args.gb * 1e9 / 100 / args.maps)
     runs = [m[0] for m in n.generate_runs("secondary", args.maps, 1, rows, 5)]
@@ -206,6 +209,41 @@ def decode(args) -> dict:
             "raw_gb": round(raw / 1e9, 3), "ratio": round(raw / comp, 2), "blocks": blocks,
             "device_decode_ms": round(ms, 1), "device_gbps_raw": round(raw / ms / 1e6, 1),
             "host_1thread_gbps_raw": round(raw / host_s / 1e9, 3), "host_compress_s": round(comp_s, 1)}
+
+
+def decode_zlib(args, n) -> dict:
+    """Device inflate of DefaultCodec partitions, one wave per stream: the launch's raw GB/s for --maps streams
+    (64 and 1024 are the recorded shapes) of TeraSort partitions and of wordcount partitions of --gb in all,
+    the Adler-32 kernel's rate over the decoded bytes, and the yardstick that is not ours: Python's
+    zlib.decompress over the same streams on one core, and that rate x 16."""
+    import zlib
+    out = {"config": f"device zlib inflate, {args.maps} streams, one wave per stream", "streams": args.maps}
+    rows = max(1, int(args.gb * 1e9 / 100 / args.maps))
+    distinct = min(args.maps, 32)  # (the streams repeat these partitions: the generator is the slow part)
+    for kind in ("terasort", "wordcount"):
+        parts = [m[0] for m in n.generate_runs(kind, distinct, 1, rows, 5)]
+        raws = [parts[i % distinct] for i in range(args.maps)]
+        packed = [zlib.compress(p) for p in parts]
+        streams = [packed[i % distinct] for i in range(args.maps)]
+        raw = sum(len(r) for r in raws)
+        n.gpu_inflate_streams(streams[:1], [len(raws[0])])  # warm up
+        best = None
+        for _ in range(3):
+            outs, consumed, ms = n.gpu_inflate_streams(streams, [len(r) for r in raws])
+            best = ms if best is None else min(best, ms)
+        assert outs == raws and consumed == [len(s) for s in streams]
+        _, adler_ms = n.gpu_adler32(raws, 0, 0, True)
+        _, adler_ms = n.gpu_adler32(raws, 0, 0, True)
+        t0 = time.perf_counter()
+        for s in packed:
+            zlib.decompress(s)
+        host_s = (time.perf_counter() - t0) * args.maps / distinct
+        host = raw / host_s / 1e9
+        out[kind] = {"raw_gb": round(raw / 1e9, 3), "ratio": round(raw / sum(len(s) for s in streams), 2),
+                     "device_inflate_and_adler_ms": round(best, 2), "device_gbps_raw": round(raw / best / 1e6, 2),
+                     "adler_ms": round(adler_ms, 2), "adler_gbps": round(raw / adler_ms / 1e6, 1),
+                     "system_zlib_1core_gbps_raw": round(host, 3), "system_zlib_x16_gbps_raw": round(host * 16, 2)}
+    return out
 
 
 def netmerger(args) -> dict:
@@ -754,7 +792,7 @@ def main() -> int:
     ap.add_argument("config", choices=["wordcount_loopback", "wordcount_tcp", "cpu_reference", "secondary_sort", "spill", "decode", "aio",
                                        "netmerger", "radix", "hybrid_budget", "combine", "combine_kernels", "checksum", "key_order"])
     ap.add_argument("--dir", default="/tmp")
-    ap.add_argument("--codec", default="snappy", choices=["snappy", "lzo", "lz4"])
+    ap.add_argument("--codec", default="snappy", choices=["snappy", "lzo", "lz4", "zlib"])
     ap.add_argument("--gb", type=float, default=1.0)
     ap.add_argument("--maps", type=int, default=16)
     ap.add_argument("--reducers", type=int, default=4)

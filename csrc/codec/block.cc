@@ -13,6 +13,9 @@ Codec codec_from_class(const std::string& cls, bool* unsupported) {
   if (cls.find("SnappyCodec") != std::string::npos) return Codec::kSnappy;
   if (cls.find("LzoCodec") != std::string::npos || cls.find("LzopCodec") != std::string::npos) return Codec::kLzo;
   if (cls.find("Lz4Codec") != std::string::npos) return Codec::kLz4;  // beyond the reference
+  // what mapreduce.map.output.compress=true alone selects; DeflateCodec is the same codec by another name.
+  // Beyond the reference too. (GzipCodec extends DefaultCodec in Java but writes another container.)
+  if (cls.find("DefaultCodec") != std::string::npos || cls.find("DeflateCodec") != std::string::npos) return Codec::kZlib;
   *unsupported = true;  // getCompAlg (reducer.cc:439-450) throws on anything else
   return Codec::kNone;
 }
@@ -22,6 +25,7 @@ const char* codec_name(Codec c) {
     case Codec::kSnappy: return "snappy";
     case Codec::kLzo: return "lzo1x";
     case Codec::kLz4: return "lz4";
+    case Codec::kZlib: return "zlib";
     default: return "none";
   }
 }
@@ -64,7 +68,12 @@ std::vector<uint8_t> block_compress(Codec c, const uint8_t* src, size_t n, size_
   return out;
 }
 
+BlockDecoder::BlockDecoder(Codec c) : codec_(c) {
+  if (c == Codec::kZlib) zlib_ = std::make_unique<Inflater>();
+}
+
 void BlockDecoder::feed(const uint8_t* p, size_t n) {
+  if (zlib_) return zlib_->feed(p, n);
   if (in_pos_ > 0 && in_pos_ == in_.size()) {
     in_.clear();
     in_pos_ = 0;
@@ -112,6 +121,7 @@ bool BlockDecoder::decode_some() {
 }
 
 size_t BlockDecoder::read(uint8_t* dst, size_t cap) {
+  if (zlib_) return zlib_->read(dst, cap);
   while (out_pos_ == out_.size()) {
     if (!decode_some()) return 0;
   }

@@ -573,7 +573,18 @@ bool ReduceTask::merge_gpu_device(bool probe) {
     // (the framing walk finds the trailers; the checksum kernels go between its two passes, and the second
     // pass's synchronize brings their result)
     std::vector<int> tails;
-    const bool dev_frames = gpu::plan_block_streams_device(codec_, cp, cl, &bp, ws.frame_scratch, ws.frame_descs, s,
+    // zlib (DefaultCodec): a partition is one stream with no framing, so there is nothing to walk and no
+    // per-round decode; the index's raw lengths lay the outputs out, and the trailers are found by the decode
+    gpu::StreamPlan zplan;
+    bool dev_inflate = false;
+    int64_t streams = 0;
+    if (codec_ == Codec::kZlib) {
+      std::vector<int64_t> raws;
+      for (const auto& p : parts) raws.push_back(p->raw_len);
+      dev_inflate = gpu::plan_zlib_streams(cp, cl, raws, &zplan);
+    }
+    const bool dev_frames = codec_ != Codec::kZlib &&
+                            gpu::plan_block_streams_device(codec_, cp, cl, &bp, ws.frame_scratch, ws.frame_descs, s,
                                                            &tails, launch_checksums);
     if (dev_frames) {
       finish_checksums(!bp.descs.empty());
@@ -630,10 +641,10 @@ bool ReduceTask::merge_gpu_device(bool probe) {
         return true;
       }
     }
-    if (dev_frames) {
+    if (dev_frames || dev_inflate) {
       // decode output and the merge's rounds at once: a task holding its decoded partitions must
       // not then wait for merge memory behind tasks doing the same
-      const int64_t raw = bp.raw_total;
+      const int64_t raw = dev_inflate ? zplan.raw_total : bp.raw_total;
       gpu::DeviceReduceConfig pcfg;  // the merge below packs its delivery: the packed slots count too
       pcfg.kv_buf_bytes = kv_buf_size_;
       pcfg.pack_version = delivery_pack_;
@@ -653,13 +664,41 @@ bool ReduceTask::merge_gpu_device(bool probe) {
         throw UdaError("reduce task stopped while waiting for a device decode slot");
       dgate.device = device;
     }
-    if (dev_frames) {
+    if (dev_inflate) {
+      DeviceWorkspace::ensure(ws.in, zplan.raw_total);
+      std::vector<std::string> ids;
+      for (const auto& p : parts) ids.push_back(p->map_id);
+      int bad = -1;
+      std::string why;
+      ws.inflater.decode(zplan, nullptr, ws.in.as<uint8_t>(), ids, s, &tails, &bad, &why);
+      if (bad >= 0) {
+        // a stream that does not decode has no known end. Where the task's other partitions carry a trailer,
+        // so does this one: its CRC tells a partition damaged on its way (the checksum mismatch, as for every
+        // other codec) from a stream that was written wrong (the decoder's own message)
+        bool trailers_seen = false;
+        for (int t : tails) trailers_seen = trailers_seen || t == kIFileChecksumBytes;
+        if (verify && trailers_seen && cl[(size_t)bad] > kIFileChecksumBytes) {
+          std::vector<int> only(parts.size(), 0);
+          only[(size_t)bad] = kIFileChecksumBytes;
+          launch_checksums(only);
+          finish_checksums(false);
+        }
+        throw UdaError(why);
+      }
+      // only now are the tails known: the checksums run over the partitions as fetched and are read here,
+      // before the merge below delivers a record
+      launch_checksums(tails);
+      finish_checksums(false);
+      roff = zplan.raw_offset;
+      streams = (int64_t)zplan.descs.size();
+    } else if (dev_frames) {
       DeviceWorkspace::ensure(ws.in, bp.raw_total);
       ws.decoder.decode(codec_, bp, nullptr, ws.in.as<uint8_t>(), s);
       roff = bp.raw_offset;
       blocks = (int64_t)bp.descs.size();
     } else {  // framing that needs a decode (multi-chunk LZO or LZ4 blocks): decode on the host
-      UDA_LOG(kInfo, "device decode: framing needs a host decode (%s)", codec_name(codec_));
+      UDA_LOG(kInfo, "device decode: %s needs a host decode (%s)",
+              codec_ == Codec::kZlib ? "a partition of unknown or 2 GiB raw length" : "framing", codec_name(codec_));
       std::vector<std::vector<uint8_t>> raws;
       roff.assign(1, 0);
       for (size_t i = 0; i < cp.size(); ++i) {
@@ -694,6 +733,7 @@ bool ReduceTask::merge_gpu_device(bool probe) {
     HIP_CHECK(hipStreamSynchronize(s));  // (the merge below syncs it anyway): decode time on its own
     std::lock_guard<std::mutex> g(st_mu_);
     st_.device_decoded_blocks += blocks;
+    st_.device_decoded_streams += streams;
     st_.gpu_decode_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - td).count();
   }
   // ---- TeraSort-shaped input: FIXED10 rounds straight over the partitions

@@ -168,7 +168,7 @@ class StagedMerge {
   void lpq_wait();
   void merge_spill(std::vector<Span> jg, std::vector<std::string> ids, EarlyStager* st);
   void index_spans(const std::vector<Span>& spans, size_t first, std::vector<SpillRun>* out) const;
-  void count_decoded(int64_t n);
+  void count_decoded(const DeviceMergeOut& m);
   void count_checksums(const DeviceMergeOut& m);
   int span_id(const std::string& map_id);
   // delivery
@@ -806,9 +806,10 @@ void StagedMerge::spill_group() {
   });
 }
 
-void StagedMerge::count_decoded(int64_t n) {
+void StagedMerge::count_decoded(const DeviceMergeOut& m) {
   std::lock_guard<std::mutex> g(t_.st_mu_);
-  t_.st_.device_decoded_blocks += n;
+  t_.st_.device_decoded_blocks += m.decoded_blocks;
+  t_.st_.device_decoded_streams += m.decoded_streams;
 }
 
 // trailers a device merge stripped from its runs (compressed runs: found by its framing walk; uncompressed
@@ -854,7 +855,7 @@ void StagedMerge::merge_spill(std::vector<Span> jg, std::vector<std::string> ids
     trace::host_event("lpq_flush", (int64_t)jg.size(), 0, tl, tm);
     trace::host_event("lpq_merge", m.bytes, (int64_t)jg.size(), tm, trace::now_ns());
   }
-  count_decoded(m.decoded_blocks);
+  count_decoded(m);
   if (st) st->reset();  // the merge read the staged copies; recycle their HBM
   SpillRun run;
   run.bytes = m.bytes;
@@ -1250,7 +1251,7 @@ void StagedMerge::run_online() {
                                   t_.merge_round_bytes_, &verify_ck_);
   count_checksums(m);
   combine_in_ += m.records_in;
-  count_decoded(m.decoded_blocks);
+  count_decoded(m);
 }
 
 // read [off, off+len) of a spilled run into dst

@@ -146,12 +146,28 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
       throw UdaError("compressed map output " + name_of(in_runs[i]) + " decodes to " + std::to_string(decoded) +
                      " bytes, its index says " + std::to_string(in_runs[i].raw_len));
   };
+  // zlib (DefaultCodec): no framing to walk. One inflate descriptor per run from the index's raw lengths; the
+  // runs' ends, and with them their trailers, are known only once they are decoded (below, behind the copies).
+  gpu::StreamPlan zplan;
+  bool inflate_on_device = false;
+  if (codec == Codec::kZlib) {
+    std::vector<int64_t> raws;
+    for (const Span& sp : in_runs) raws.push_back(sp.raw_len);
+    inflate_on_device = gpu::plan_zlib_streams({}, lens, raws, &zplan);
+    if (inflate_on_device) {
+      plan.raw_offset = zplan.raw_offset;
+      plan.raw_total = zplan.raw_total;
+    }
+  }
   if (codec != Codec::kNone) {
-    decode_on_device = gpu::plan_block_streams(codec, ptrs, lens, &plan, &tails);
-    if (decode_on_device)
+    decode_on_device = inflate_on_device || (codec != Codec::kZlib && gpu::plan_block_streams(codec, ptrs, lens, &plan, &tails));
+    if (decode_on_device && !inflate_on_device)
       for (size_t i = 0; i < ptrs.size(); ++i) check_raw_len(i, plan.raw_offset[i + 1] - plan.raw_offset[i]);
     if (!decode_on_device) {
-      UDA_LOG(kInfo, "device decode: framing needs a host decode (multi-chunk %s block)", codec_name(codec));
+      if (codec == Codec::kZlib)
+        UDA_LOG(kInfo, "device decode: a zlib partition of unknown or 2 GiB raw length needs a host decode");
+      else
+        UDA_LOG(kInfo, "device decode: framing needs a host decode (multi-chunk %s block)", codec_name(codec));
       for (size_t i = 0; i < ptrs.size(); ++i) {
         // (the bytes are decoded here, on the host: so is their checksum)
         std::vector<uint8_t> raw = host_decode_partition(codec, ptrs[i], lens[i], &tails[i]);
@@ -243,7 +259,53 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
   ws.h2d_ms += std::chrono::duration<double, std::milli>(t1 - t0).count();
   const int64_t tm = trace::host_enabled() ? trace::now_ns() : 0;
   if (tm) trace::host_event("dm_h2d", staged, (int64_t)ptrs.size(), tm - (int64_t)((t1 - t0).count()), tm);
-  if (decode_on_device) {
+  if (inflate_on_device) {
+    std::vector<gpu::DeviceChecksum::Item> zitems;  // (`items` may have been moved from above)
+    std::vector<std::string> ids;
+    for (const Span& sp : in_runs) ids.push_back(name_of(sp));
+    int bad = -1;
+    std::string why;
+    ws.inflater.decode(zplan, ws.packed.as<uint8_t>(), in.as<uint8_t>(), ids, s, &tails, &bad, &why);
+    if (bad >= 0) {
+      // a stream that does not decode has no known end. Where the merge's other runs carry a trailer, so does
+      // this one: its CRC tells a run damaged on its way (the checksum mismatch, as for every other codec) from
+      // a stream that was written wrong (the decoder's own message)
+      bool trailers_seen = false;
+      for (int t : tails) trailers_seen = trailers_seen || t == kIFileChecksumBytes;
+      const size_t b = (size_t)bad;
+      if (verify && trailers_seen && lens[b] > kIFileChecksumBytes) {
+        int64_t boff = 0;
+        for (size_t i = 0; i < b; ++i) boff += lens[i];
+        const int64_t body = lens[b] - kIFileChecksumBytes;
+        zitems.push_back(gpu::DeviceChecksum::Item{ws.packed.as<uint8_t>() + boff, body, name_of(in_runs[b]), true,
+                                                  ifile_stored_checksum(ptrs[b] + body)});
+        ws.checksum.reset();
+        ws.checksum.launch(std::move(zitems), s);
+        ws.checksum.finish(s, false);
+      }
+      throw UdaError(why);
+    }
+    res.decoded_streams = (int64_t)zplan.descs.size();
+    // the tails are known now: the IFile checksums over the bytes as staged, verified before the merge below
+    // hands a record over (the stored value from the host copy)
+    int64_t zoff = 0;
+    for (size_t i = 0; i < ptrs.size(); ++i) {
+      if (tails[i]) {
+        ++res.trailers;
+        const int64_t body = lens[i] - tails[i];
+        if (verify)
+          zitems.push_back(gpu::DeviceChecksum::Item{ws.packed.as<uint8_t>() + zoff, body, name_of(in_runs[i]), true,
+                                                    ifile_stored_checksum(ptrs[i] + body)});
+      }
+      zoff += lens[i];
+    }
+    if (!zitems.empty()) {
+      ws.checksum.reset();
+      ws.checksum.launch(std::move(zitems), s);
+      ws.checksum.finish(s, false);
+      verified();
+    }
+  } else if (decode_on_device) {
     ws.decoder.decode(codec, plan, ws.packed.as<uint8_t>(), in.as<uint8_t>(), s);
     res.decoded_blocks = (int64_t)plan.descs.size();
   }

@@ -314,6 +314,16 @@ int64_t MofFetcher::pull(uint8_t* dst, int64_t cap) {
           throw UdaError("compressed map output " + p_.map_id + " decodes to " + std::to_string(decoded_) +
                          " bytes, its index says " + std::to_string(raw_len_));
         check_trailer();
+      } else if (!tail_decided_ && seen_ >= part_len_ && dec_->starved()) {
+        // a zlib stream without a trailer: the held-back bytes are its own Adler-32, which the decoder has not
+        // seen. It is checked now, before the consumer sees the EOF marker in these bytes and stops reading
+        tail_decided_ = true;
+        dec_->feed(stored_, (size_t)stored_n_);
+        (void)dec_->read(dst + r, 0);  // (no output is left: this reads the stream's end, or throws)
+        if (!dec_->idle()) throw UdaError("compressed MOF " + p_.map_id + " ended inside its zlib stream");
+        if (raw_len_ > 0 && decoded_ != raw_len_)
+          throw UdaError("compressed map output " + p_.map_id + " decodes to " + std::to_string(decoded_) +
+                         " bytes, its index says " + std::to_string(raw_len_));
       }
       return (int64_t)r;
     }
@@ -1104,6 +1114,7 @@ std::string ReduceTask::stats_json() const {
     << ",\"records\":" << s.records << ",\"buffers\":" << s.buffers << ",\"lpqs\":" << s.lpqs
     << ",\"spill_bytes\":" << s.spill_bytes << ",\"fetch_ms\":" << s.fetch_ms << ",\"merge_ms\":" << s.merge_ms
     << ",\"total_ms\":" << s.total_ms << ",\"device_decoded_blocks\":" << s.device_decoded_blocks
+    << ",\"device_decoded_streams\":" << s.device_decoded_streams
     << ",\"rpq_rounds\":" << s.rpq_rounds << ",\"hybrid_direct\":" << s.hybrid_direct << ",\"merge_budget_from_ledger\":" << s.merge_budget_from_ledger << ",\"gpu_h2d_ms\":" << s.gpu_h2d_ms
     << ",\"gpu_device_ms\":" << s.gpu_device_ms << ",\"gpu_d2h_wait_ms\":" << s.gpu_d2h_wait_ms
     << ",\"gpu_sink_ms\":" << s.gpu_sink_ms << ",\"gpu_d2h_bytes\":" << s.gpu_d2h_bytes << ",\"gpu_packed_pieces\":" << s.gpu_packed_pieces

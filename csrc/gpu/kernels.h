@@ -345,6 +345,44 @@ void launch_frame_streams(const uint8_t* const* ptrs, const int64_t* lens, int n
                           const int64_t* desc_first, const int64_t* raw_first, int64_t* nblocks, int64_t* raw,
                           DecodeDesc* out, int* status, hipStream_t s, int* tails = nullptr);
 
+// ---------------------------------------------------------------- zlib inflate (DefaultCodec), inflate.hip
+// One zlib stream (RFC 1950: a partition as DefaultCodec's CompressorStream wrote it) per descriptor, decoded
+// by one wave64. src is an offset into `in`, or an absolute address when in == nullptr (as DecodeDesc); dst is
+// an offset into `out`. At most raw_len bytes are written at dst and no byte at or past src + src_len is read.
+// Streams and outputs are below 2 GiB each (status kInflateTooBig otherwise: decode those on the host).
+struct InflateDesc {
+  int64_t src, src_len, dst, raw_len;
+};
+// consumed: bytes of src the stream took, header to Adler-32; produced: bytes written; adler_stored: the
+// stream's own Adler-32 (not verified here: launch_adler32 over the output, compared on the host).
+// status 0 = the stream ended after BFINAL with its Adler-32 read; produced may still differ from raw_len.
+struct InflateResult {
+  int64_t consumed, produced;
+  uint32_t adler_stored;
+  int status;
+};
+enum InflateStatus : int {
+  kInflateOk = 0,
+  kInflateCorrupt = 1,    // a stream zlib's inflate refuses
+  kInflateTruncated = 2,  // the bit position ran past src_len
+  kInflateOverflow = 3,   // more output than raw_len
+  kInflateTooBig = 4,
+};
+void launch_inflate_streams(const uint8_t* in, uint8_t* out, const InflateDesc* d, int n, InflateResult* r, hipStream_t s);
+// Constants of the kernel for tests that lay codes on its boundaries: the register input window and the
+// alignment of its base, the literals staged in registers before one store, waves (streams) per workgroup,
+// LDS bytes per wave.
+struct InflateGeometry {
+  int window, window_align, literal_stage, waves_per_block, lds_per_wave;
+};
+InflateGeometry inflate_geometry();
+
+// ---------------------------------------------------------------- Adler-32 of device-resident byte ranges
+// zlib's adler32() of n ranges in one launch (adler32.hip). ptrs / lens / out are device arrays of n; work is
+// 2 * n uint64 of device scratch (zeroed here). A range is summed by several workgroups, whose partial sums
+// are combined on the device (Adler-32 of a concatenation from the pieces' sums and their distances to the end).
+void launch_adler32(const uint8_t* const* ptrs, const int64_t* lens, int n, uint32_t* out, uint64_t* work, hipStream_t s);
+
 // ---------------------------------------------------------------- CRC32 of device-resident byte ranges
 // zlib's crc32() of n byte ranges in one batched launch (crc32.hip): the IFile checksum of fetched
 // partitions (uda/ifile.h). A range is cut into chunks of crc32_chunk_bytes() at 16-byte-aligned

@@ -1,0 +1,115 @@
+// zlib stream plan and device decode: see stream_decoder.h.
+#include "stream_decoder.h"
+
+#include <cstdio>
+#include <cstring>
+
+#include "uda/error.h"
+#include "uda/ifile.h"
+#include "uda/trace.h"
+
+namespace uda {
+namespace gpu {
+
+bool plan_zlib_streams(const std::vector<const uint8_t*>& ptrs, const std::vector<int64_t>& lens,
+                       const std::vector<int64_t>& raw_lens, StreamPlan* plan) {
+  constexpr int64_t kLimit = 1ll << 31;  // the kernel's positions are 32-bit
+  plan->descs.clear();
+  plan->raw_offset.assign(1, 0);
+  plan->raw_total = 0;
+  int64_t in_off = 0, raw = 0;
+  for (size_t i = 0; i < lens.size(); ++i) {
+    if (raw_lens[i] <= 0 || raw_lens[i] >= kLimit || lens[i] >= kLimit) return false;
+    const int64_t src = ptrs.empty() ? in_off : (int64_t)reinterpret_cast<uintptr_t>(ptrs[i]);
+    plan->descs.push_back(InflateDesc{src, lens[i], raw, raw_lens[i]});
+    in_off += lens[i];
+    raw += raw_lens[i];
+    plan->raw_offset.push_back(raw);
+  }
+  plan->raw_total = raw;
+  return true;
+}
+
+namespace {
+const char* status_text(int st) {
+  switch (st) {
+    case kInflateTruncated: return "truncated";
+    case kInflateOverflow: return "more output than its index says";
+    case kInflateTooBig: return "2 GiB or more";
+    default: return "refused";
+  }
+}
+size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+}  // namespace
+
+void DeviceStreamDecoder::decode(const StreamPlan& plan, const uint8_t* d_in, uint8_t* d_out,
+                                 const std::vector<std::string>& ids, hipStream_t s, std::vector<int>* tails,
+                                 int* failed, std::string* why) {
+  const int n = (int)plan.descs.size();
+  if (failed) *failed = -1;
+  if (tails) tails->assign((size_t)n, 0);
+  results_.assign((size_t)n, InflateResult{});
+  if (n == 0) return;
+  trace::Range tr("uda.inflate_streams");
+  // scratch: descs | results | out ptrs | out lens | adler out | adler work
+  const size_t o_desc = 0, o_res = up16(o_desc + (size_t)n * sizeof(InflateDesc));
+  const size_t o_ptr = up16(o_res + (size_t)n * sizeof(InflateResult)), o_len = o_ptr + (size_t)n * 8;
+  const size_t o_adler = up16(o_len + (size_t)n * 8), o_work = up16(o_adler + (size_t)n * 4);
+  const size_t bytes = o_work + (size_t)n * 16;
+  if (scratch_.size() < bytes) scratch_.alloc(bytes + bytes / 2);
+  uint8_t* const base = scratch_.as<uint8_t>();
+  std::vector<const uint8_t*> optr((size_t)n);
+  std::vector<int64_t> olen((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    optr[(size_t)i] = d_out + plan.descs[(size_t)i].dst;
+    olen[(size_t)i] = plan.descs[(size_t)i].raw_len;
+  }
+  HIP_CHECK(hipMemcpyAsync(base + o_desc, plan.descs.data(), (size_t)n * sizeof(InflateDesc), hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(base + o_ptr, optr.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(base + o_len, olen.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemsetAsync(base + o_res, 0xFF, (size_t)n * sizeof(InflateResult), s));  // (a status no wave wrote reads as an error)
+  launch_inflate_streams(d_in, d_out, reinterpret_cast<const InflateDesc*>(base + o_desc), n,
+                         reinterpret_cast<InflateResult*>(base + o_res), s);
+  HIP_CHECK(hipGetLastError());
+  // the format's own integrity check, always on: over the bytes just decoded, in the same pass over s
+  launch_adler32(reinterpret_cast<const uint8_t* const*>(base + o_ptr), reinterpret_cast<const int64_t*>(base + o_len), n,
+                 reinterpret_cast<uint32_t*>(base + o_adler), reinterpret_cast<uint64_t*>(base + o_work), s);
+  HIP_CHECK(hipGetLastError());
+  std::vector<uint32_t> adler((size_t)n);
+  HIP_CHECK(hipMemcpyAsync(results_.data(), base + o_res, (size_t)n * sizeof(InflateResult), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(adler.data(), base + o_adler, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  auto check = [&](int i) -> std::string {  // "" = stream i is good, its tail filled in
+    const InflateResult& r = results_[(size_t)i];
+    const InflateDesc& d = plan.descs[(size_t)i];
+    const std::string id = (size_t)i < ids.size() ? ids[(size_t)i] : "#" + std::to_string(i);
+    if (r.status != kInflateOk)
+      return "corrupt zlib stream in map output " + id + " (" + status_text(r.status) + ", device inflate)";
+    if (r.produced != d.raw_len)
+      return "compressed map output " + id + " decodes to " + std::to_string(r.produced) + " bytes, its index says " +
+             std::to_string(d.raw_len);
+    if (r.adler_stored != adler[(size_t)i]) {
+      char buf[64];
+      std::snprintf(buf, sizeof buf, "stored 0x%08x, computed 0x%08x", r.adler_stored, adler[(size_t)i]);
+      return "zlib Adler-32 mismatch in map output " + id + ": " + buf;
+    }
+    const int64_t tail = d.src_len - r.consumed;
+    if (tail != 0 && tail != kIFileChecksumBytes)
+      return "corrupt zlib stream in map output " + id + ": " + std::to_string(tail) +
+             " bytes behind its end (an IFile checksum has " + std::to_string(kIFileChecksumBytes) + ")";
+    if (tails) (*tails)[(size_t)i] = (int)tail;
+    return std::string();
+  };
+  for (int i = 0; i < n; ++i) {
+    const std::string err = check(i);
+    if (err.empty()) continue;
+    if (!failed) throw UdaError(err);
+    if (*failed < 0) {
+      *failed = i;
+      if (why) *why = err;
+    }
+  }
+}
+
+}  // namespace gpu
+}  // namespace uda

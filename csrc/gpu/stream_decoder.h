@@ -1,0 +1,53 @@
+// Host side of the zlib (DefaultCodec) device decode: one inflate descriptor per partition and the launches
+// of csrc/gpu/inflate.hip and adler32.hip. The sibling of block_decoder.h for the codec that has no blocks:
+// a partition is one zlib stream, its raw size comes from the index and its end (and with it whether an IFile
+// checksum trailer follows) is known only once it has been decoded.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "device_engine.h"
+#include "kernels.h"
+
+namespace uda {
+namespace gpu {
+
+struct StreamPlan {
+  std::vector<InflateDesc> descs;   // one per stream, outputs back to back
+  std::vector<int64_t> raw_offset;  // per stream: first raw byte (size streams + 1)
+  int64_t raw_total = 0;
+};
+
+// Streams of lens[i] bytes that decode to raw_lens[i] bytes (the index's rawLength). ptrs given: absolute
+// device addresses (decode with d_in = nullptr); ptrs empty: stream i lies at sum(lens[<i]) of one buffer.
+// false: a raw length is unknown (<= 0), or a stream or its output is 2 GiB or more: the caller decodes on
+// the host.
+bool plan_zlib_streams(const std::vector<const uint8_t*>& ptrs, const std::vector<int64_t>& lens,
+                       const std::vector<int64_t>& raw_lens, StreamPlan* plan);
+
+class DeviceStreamDecoder {
+ public:
+  // Inflate every stream of the plan into d_out and sum the decoded bytes (Adler-32) in the same pass over
+  // the stream s; synchronizes s. ids[i] names map output i in the errors (may be short: "#i" then). Throws
+  // UdaError: "corrupt zlib stream in map output <id>" (truncated streams and output past the raw length
+  // included, the reason in brackets), "compressed map output <id> decodes to N bytes, its index says M",
+  // "zlib Adler-32 mismatch in map output <id>: stored 0x..., computed 0x...", and a malformed tail.
+  // tails[i] = bytes of stream i behind its Adler-32: 0, or 4 (an IFile checksum trailer).
+  // failed (optional): instead of throwing, the first stream in error is reported there with its message in
+  // *why (-1: none) and the other streams' tails are still filled in. A stream that does not decode has no
+  // known end, so the caller that verifies IFile checksums can first hold that partition's bytes against the
+  // trailer its neighbours show it to have, and report a partition damaged on its way as a checksum mismatch.
+  void decode(const StreamPlan& plan, const uint8_t* d_in, uint8_t* d_out, const std::vector<std::string>& ids,
+              hipStream_t s, std::vector<int>* tails, int* failed = nullptr, std::string* why = nullptr);
+  const std::vector<InflateResult>& results() const { return results_; }
+
+ private:
+  DeviceBuffer scratch_;
+  std::vector<InflateResult> results_;
+};
+
+}  // namespace gpu
+}  // namespace uda

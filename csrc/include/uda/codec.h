@@ -11,15 +11,20 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
 namespace uda {
 
-enum class Codec { kNone = 0, kSnappy = 1, kLzo = 2, kLz4 = 3 };
+// kZlib (Hadoop's DefaultCodec / DeflateCodec) is no block codec: a partition is one RFC 1950 zlib stream
+// with no framing, so block_compress, plan_block_streams* and launch_block_decode refuse it and the
+// inflate entry points below (and csrc/gpu/inflate.hip) take it. Beyond the reference, like LZ4.
+enum class Codec { kNone = 0, kSnappy = 1, kLzo = 2, kLz4 = 3, kZlib = 4 };
 
-// Map a Hadoop codec class name ("...SnappyCodec", "...LzoCodec", "...Lz4Codec") to a codec; kNone for ""/null.
-// Unsupported names return kNone and set *unsupported.
+// Map a Hadoop codec class name ("...SnappyCodec", "...LzoCodec", "...Lz4Codec", "...DefaultCodec",
+// "...DeflateCodec") to a codec; kNone for ""/null. Unsupported names (Gzip, BZip2, ZStandard ...) return
+// kNone and set *unsupported.
 Codec codec_from_class(const std::string& cls, bool* unsupported);
 const char* codec_name(Codec c);
 
@@ -40,25 +45,76 @@ size_t lz4_max_compressed_length(size_t n);
 size_t lz4_compress(const uint8_t* src, size_t n, uint8_t* dst);
 bool lz4_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len);
 
+// ---- zlib (RFC 1950 stream around RFC 1951 deflate: what DefaultCodec's CompressorStream writes, one
+// stream per partition). Decode only; csrc/codec/inflate.cc. Refuses what zlib's inflate refuses.
+// One shot: decodes the stream at src into dst[0, cap); *consumed = bytes of src the stream took (header
+// to Adler-32). false: corrupt, truncated, Adler-32 mismatch, or more than cap bytes of output.
+bool zlib_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len, size_t* consumed);
+
+// Incremental: feed compressed bytes in arbitrary pieces, read raw. Memory is a 32 KiB history plus a
+// fixed output buffer however long the stream is. The decoder restarts at unit boundaries: it commits its
+// bit position only after a whole block header (a dynamic header's code lengths included), a whole symbol
+// with its extra bits, or a chunk of a stored block, and otherwise waits for more input.
+class Inflater {
+ public:
+  Inflater();
+  void feed(const uint8_t* p, size_t n);
+  // Copy up to `cap` decoded bytes into dst; 0 = needs more input, or the stream has ended.
+  // Throws UdaError ("corrupt zlib stream: ...") on a stream zlib's inflate would refuse.
+  size_t read(uint8_t* dst, size_t cap);
+  bool finished() const { return state_ == kDone; }  // the Adler-32 was read and matched
+  // Stream finished, no buffered output, no unconsumed input.
+  bool idle() const { return finished() && rpos_ == wpos_ && (bitpos_ + 7) / 8 == in_.size(); }
+  // After a read(): nothing is buffered and the stream has not ended: it needs more input.
+  bool starved() const { return !finished() && rpos_ == wpos_; }
+  uint64_t consumed() const { return dropped_ + (bitpos_ + 7) / 8; }  // input bytes the stream took so far
+
+ private:
+  enum State { kHeader, kBlockHeader, kStored, kSymbols, kAdler, kDone };
+  void run();  // decode until the output buffer is full, the input runs out or the stream ends
+  void fail(const char* what) const;
+  void slide();
+  void sum();
+  std::vector<uint8_t> in_;
+  uint64_t bitpos_ = 0;   // next unread bit of in_
+  uint64_t dropped_ = 0;  // input bytes already dropped from in_
+  std::vector<uint8_t> buf_;  // history + output: [0, wpos_) decoded, [rpos_, wpos_) not yet read
+  size_t wpos_ = 0, rpos_ = 0, spos_ = 0;  // spos_: the Adler-32 covers [.., spos_)
+  uint64_t total_out_ = 0;
+  uint32_t adler_a_ = 1, adler_b_ = 0;
+  State state_ = kHeader;
+  bool last_ = false;
+  uint32_t stored_left_ = 0;
+  std::vector<uint16_t> lit_, dist_;
+};
+
 // Compress `n` bytes into Hadoop block framing with blocks of at most `block_size` raw bytes.
 std::vector<uint8_t> block_compress(Codec c, const uint8_t* src, size_t n, size_t block_size);
 
 // Incremental decoder of a framed stream: feed compressed bytes in arbitrary pieces, read raw.
 class BlockDecoder {
  public:
-  explicit BlockDecoder(Codec c) : codec_(c) {}
+  explicit BlockDecoder(Codec c);
   // Append compressed input.
   void feed(const uint8_t* p, size_t n);
   // Copy up to `cap` decoded bytes into dst; returns bytes produced (0 = need more input).
   // Throws UdaError on a corrupt stream.
   size_t read(uint8_t* dst, size_t cap);
-  // True when no buffered raw bytes remain and the input ended on a block boundary.
-  bool idle() const { return out_pos_ == out_.size() && in_.size() == in_pos_ && block_remaining_ == 0; }
+  // True when no buffered raw bytes remain and the input ended on a block boundary (kZlib: the stream
+  // ended, with no input behind it).
+  bool idle() const {
+    if (zlib_) return zlib_->idle();
+    return out_pos_ == out_.size() && in_.size() == in_pos_ && block_remaining_ == 0;
+  }
+  // kZlib only: every decoded byte was read and the stream has not ended, so it waits for input (a block
+  // codec's blocks end where their framing says, and this is always false).
+  bool starved() const { return zlib_ && zlib_->starved(); }
   int64_t blocks() const { return blocks_; }
 
  private:
   bool decode_some();
   Codec codec_;
+  std::unique_ptr<Inflater> zlib_;  // kZlib: feed / read / idle go to it
   std::vector<uint8_t> in_;
   size_t in_pos_ = 0;
   std::vector<uint8_t> out_;

@@ -24,6 +24,7 @@
 #include "device_reduce.h"
 #include "fixed_delivery.h"
 #include "mof_cache.h"
+#include "consumer/gpu_workspace.h"
 #include "consumer/reduce_task.h"
 #include "service/merge_service.h"
 #include "exchange.h"
@@ -31,6 +32,7 @@
 #include "generic_merger.h"
 #include "generic_rounds.h"
 #include "j2c_sink.h"
+#include "stream_decoder.h"
 #include "stream_sampler.h"
 #include "uda/aio.h"
 #include "uda/codec.h"
@@ -855,6 +857,26 @@ PYBIND11_MODULE(_uda_native, m) {
     if (!d.idle()) throw py::value_error("truncated block stream");
     return py::bytes(out);
   });
+
+  // zlib (DefaultCodec) one-shot host decode: (raw bytes, bytes of the input the stream took). ValueError for
+  // anything zlib's inflate refuses, a truncated stream, an Adler-32 mismatch or more than cap bytes of output.
+  m.def("zlib_decompress", [](py::bytes b, size_t cap) {
+    std::string s = b;
+    std::string out(cap, '\0');
+    size_t n = 0, used = 0;
+    if (!zlib_decompress((const uint8_t*)s.data(), s.size(), (uint8_t*)&out[0], cap, &n, &used))
+      throw py::value_error("corrupt zlib data");
+    out.resize(n);
+    return py::make_tuple(py::bytes(out), used);
+  }, py::arg("data"), py::arg("cap"));
+  // A whole compressed partition as the GPU paths decode it on the host (consumer/gpu_workspace.h): all but
+  // the last four bytes first, and the decoder says whether those four are an IFile checksum. (raw, tail)
+  m.def("host_decode_partition", [](int codec, py::bytes b) {
+    std::string s = b;
+    int tail = 0;
+    std::vector<uint8_t> raw = host_decode_partition((Codec)codec, (const uint8_t*)s.data(), (int64_t)s.size(), &tail);
+    return py::make_tuple(py::bytes((const char*)raw.data(), raw.size()), tail);
+  }, py::arg("codec"), py::arg("partition"));
 
   // ---- IFile checksum trailer (uda/ifile.h)
   m.def("crc32", [](py::bytes b, uint32_t seed) {
@@ -2532,6 +2554,125 @@ PYBIND11_MODULE(_uda_native, m) {
     for (auto& o : outs) l.append(py::bytes(o));
     return py::make_tuple(py::object(l), blocks, ms);
   }, py::arg("codec"), py::arg("streams"), py::arg("device") = 0, py::arg("clip") = 0);
+  // zlib streams inflated on the device in one launch (gpu/stream_decoder.h): (raw streams, bytes each stream
+  // took, ms). Output i is raw_lens[i] bytes followed by 256 guard bytes of 0xA5, the whole buffer 0xA5 before
+  // the launch; a guard byte that changed is an error here whatever the decode said.
+  m.def("gpu_inflate_streams", [](const std::vector<std::string>& streams, const std::vector<int64_t>& raw_lens, int device) {
+    if (streams.size() != raw_lens.size()) throw py::value_error("one raw length per stream");
+    constexpr int64_t kGuard = 256;
+    std::vector<std::string> outs;
+    std::vector<int64_t> consumed;
+    double ms = 0;
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      gpu::StreamPlan plan;
+      plan.raw_offset.assign(1, 0);
+      int64_t staged = 0, out_bytes = 0;
+      for (size_t i = 0; i < streams.size(); ++i) {
+        if (raw_lens[i] < 0) throw UdaError("raw length < 0");
+        plan.descs.push_back(gpu::InflateDesc{staged, (int64_t)streams[i].size(), out_bytes, raw_lens[i]});
+        staged += (int64_t)streams[i].size();
+        out_bytes += raw_lens[i] + kGuard;
+        plan.raw_offset.push_back(out_bytes);
+      }
+      plan.raw_total = out_bytes;
+      gpu::DeviceBuffer din((size_t)std::max<int64_t>(staged, 16)), dout((size_t)std::max<int64_t>(out_bytes, 16));
+      hipStream_t s;
+      HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      for (size_t i = 0; i < streams.size(); ++i)
+        if (!streams[i].empty())
+          HIP_CHECK(hipMemcpyAsync(din.as<uint8_t>() + plan.descs[i].src, streams[i].data(), streams[i].size(),
+                                   hipMemcpyHostToDevice, s));
+      if (out_bytes) HIP_CHECK(hipMemsetAsync(dout.as(), 0xA5, (size_t)out_bytes, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      gpu::DeviceStreamDecoder dec;
+      std::string err;
+      auto t0 = std::chrono::steady_clock::now();
+      try {
+        dec.decode(plan, din.as<uint8_t>(), dout.as<uint8_t>(), {}, s, nullptr);
+      } catch (const UdaError& e) {
+        err = e.what();
+      }
+      ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      std::string all((size_t)out_bytes, '\0');
+      if (out_bytes) HIP_CHECK(hipMemcpyAsync(&all[0], dout.as(), all.size(), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      HIP_CHECK(hipStreamDestroy(s));
+      for (size_t i = 0; i < streams.size(); ++i) {
+        const size_t g0 = (size_t)(plan.descs[i].dst + raw_lens[i]);
+        for (size_t k = 0; k < (size_t)kGuard; ++k)
+          if ((uint8_t)all[g0 + k] != 0xA5)
+            throw UdaError("device inflate wrote past the output of stream " + std::to_string(i) + " (guard byte " +
+                           std::to_string(k) + ")");
+      }
+      if (!err.empty()) throw UdaError(err);
+      for (size_t i = 0; i < streams.size(); ++i) {
+        outs.push_back(all.substr((size_t)plan.descs[i].dst, (size_t)raw_lens[i]));
+        consumed.push_back(dec.results()[i].consumed);
+      }
+    }
+    py::list l;
+    for (auto& o : outs) l.append(py::bytes(o));
+    return py::make_tuple(py::object(l), consumed, ms);
+  }, py::arg("streams"), py::arg("raw_lens"), py::arg("device") = 0);
+  // zlib.adler32 of every item in one batched launch (gpu/adler32.hip); item i starts `misalign` bytes past a
+  // 16-byte boundary of the device buffer.
+  // timed: returns (values, ms of the launch alone, from its queueing to its result) instead.
+  m.def("gpu_adler32", [](const std::vector<std::string>& items, int misalign, int device, bool timed) -> py::object {
+    if (misalign < 0 || misalign > 15) throw py::value_error("misalign 0..15");
+    std::vector<uint32_t> out(items.size());
+    double ms = 0;
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      const int n = (int)items.size();
+      std::vector<int64_t> offs, lens;
+      int64_t total = 16;
+      for (auto& it : items) {
+        offs.push_back(total + misalign);
+        lens.push_back((int64_t)it.size());
+        total = (total + misalign + (int64_t)it.size() + 15) / 16 * 16;
+      }
+      gpu::DeviceBuffer data((size_t)total + 16), meta((size_t)std::max(n, 1) * 48);
+      std::vector<const uint8_t*> ptrs;
+      for (auto o : offs) ptrs.push_back(data.as<uint8_t>() + o);
+      hipStream_t s;
+      HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      for (int i = 0; i < n; ++i)
+        if (!items[(size_t)i].empty())
+          HIP_CHECK(hipMemcpyAsync(data.as<uint8_t>() + offs[(size_t)i], items[(size_t)i].data(), items[(size_t)i].size(),
+                                   hipMemcpyHostToDevice, s));
+      uint8_t* mb = meta.as<uint8_t>();
+      if (n) {
+        HIP_CHECK(hipMemcpyAsync(mb, ptrs.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipMemcpyAsync(mb + (size_t)n * 8, lens.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        const auto t0 = std::chrono::steady_clock::now();
+        gpu::launch_adler32(reinterpret_cast<const uint8_t* const*>(mb), reinterpret_cast<const int64_t*>(mb + (size_t)n * 8), n,
+                            reinterpret_cast<uint32_t*>(mb + (size_t)n * 16), reinterpret_cast<uint64_t*>(mb + (size_t)n * 32), s);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(out.data(), mb + (size_t)n * 16, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      }
+      HIP_CHECK(hipStreamSynchronize(s));
+      HIP_CHECK(hipStreamDestroy(s));
+    }
+    if (timed) return py::make_tuple(out, ms);
+    return py::cast(out);
+  }, py::arg("items"), py::arg("misalign") = 0, py::arg("device") = 0, py::arg("timed") = false);
+  // The inflate kernel's constants (needs no GPU), for tests that lay codes on its boundaries.
+  m.def("gpu_inflate_geometry", []() {
+    const gpu::InflateGeometry g = gpu::inflate_geometry();
+    py::dict d;
+    d["window"] = g.window;
+    d["window_align"] = g.window_align;
+    d["literal_stage"] = g.literal_stage;
+    d["waves_per_block"] = g.waves_per_block;
+    d["lds_per_wave"] = g.lds_per_wave;
+    return d;
+  });
   m.def("nccl_unique_id", []() { return py::bytes(gpu::nccl_unique_id()); });
   // RCCL data-plane self test on one GPU: communicator bootstrap from an ncclUniqueId and the grouped
   // send/recv counts exchange the shuffle plan uses (world 1: the rank exchanges with itself).

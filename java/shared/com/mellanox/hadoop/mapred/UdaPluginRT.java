@@ -73,7 +73,11 @@ class UdaPluginRT extends UdaPlugin implements UdaCallable {
     p.add(Long.toString(maxBufKb * 1024));
     p.add(Long.toString(minBufKb * 1024));
     p.add(conf.getMapOutputKeyClass().getName());
-    String codec = conf.getCompressMapOutput() ? conf.get("mapred.map.output.compression.codec", null) : null;
+    // the class name goes through unchanged (the native side maps it, codec_from_class). A job that only turns
+    // compression on has no codec key: Hadoop then writes with DefaultCodec
+    // (JobConf.getMapOutputCompressorClass(DefaultCodec.class)), so that is the name to send, not "null"
+    String codec = conf.getCompressMapOutput()
+        ? conf.get("mapred.map.output.compression.codec", "org.apache.hadoop.io.compress.DefaultCodec") : null;
     p.add(codec == null ? "null" : codec);
     p.add(Integer.toString(codecBlockSize(conf, codec)));
     p.add(Long.toString(shuffleMem));
