@@ -8,7 +8,7 @@
                       write_kv_to_stream packing) on TeraSort runs on this host's CPU.
   secondary_sort      variable-length Text keys with long common prefixes + partition skew: GPU generic
                       merge (F1/F2/F3/F4 kernels) vs the CPU heap merge on the same runs.
-  decode              F6 Snappy / LZO1X block decode on the device vs the host decoder; --codec zlib: the
+  decode              F6 Snappy / LZO1X block decode on the device vs the host decoder; --codec zlib / gzip: the
                       device inflate (one wave per stream, --maps streams) vs the system zlib.
   netmerger           secondary-sort data through provider -> NetMerger -> dataFromUda: CPU heap merge vs
                       GPU backend (online and hybrid LPQ/RPQ).
@@ -188,7 +188,7 @@ def decode(args) -> dict:
     """F6: device block decode of block-compressed IFile runs (secondary-sort data) vs host decode."""
     from uda_amd import native
     n = native()
-    if args.codec == "zlib":
+    if args.codec in ("zlib", "gzip"):
         return decode_zlib(args, n)
     codec = {"snappy": 1, "lzo": 2, "lz4": 3}[args.codec]
     rows = int(args.gb * 1e9 / 100 / args.maps)
@@ -215,32 +215,37 @@ def decode_zlib(args, n) -> dict:
     """Device inflate of DefaultCodec partitions, one wave per stream: the launch's raw GB/s for --maps streams
     (64 and 1024 are the recorded shapes) of TeraSort partitions and of wordcount partitions of --gb in all,
     the Adler-32 kernel's rate over the decoded bytes, and the yardstick that is not ours: Python's
-    zlib.decompress over the same streams on one core, and that rate x 16."""
+    zlib.decompress over the same streams on one core, and that rate x 16.
+    --codec gzip: the same partitions as GzipCodec members (gzip.compress, bare header); the launch's time is
+    then inflate + the CRC-32 pass over the output, and the yardstick zlib.decompress(s, 31)."""
+    import gzip
     import zlib
-    out = {"config": f"device zlib inflate, {args.maps} streams, one wave per stream", "streams": args.maps}
+    gz = args.codec == "gzip"
+    wbits = 31 if gz else 15
+    out = {"config": f"device {args.codec} inflate, {args.maps} streams, one wave per stream", "streams": args.maps}
     rows = max(1, int(args.gb * 1e9 / 100 / args.maps))
     distinct = min(args.maps, 32)  # (the streams repeat these partitions: the generator is the slow part)
     for kind in ("terasort", "wordcount"):
         parts = [m[0] for m in n.generate_runs(kind, distinct, 1, rows, 5)]
         raws = [parts[i % distinct] for i in range(args.maps)]
-        packed = [zlib.compress(p) for p in parts]
+        packed = [gzip.compress(p, 6, mtime=0) if gz else zlib.compress(p) for p in parts]
         streams = [packed[i % distinct] for i in range(args.maps)]
         raw = sum(len(r) for r in raws)
-        n.gpu_inflate_streams(streams[:1], [len(raws[0])])  # warm up
+        n.gpu_inflate_streams(streams[:1], [len(raws[0])], 0, args.codec)  # warm up
         best = None
         for _ in range(3):
-            outs, consumed, ms = n.gpu_inflate_streams(streams, [len(r) for r in raws])
+            outs, consumed, ms = n.gpu_inflate_streams(streams, [len(r) for r in raws], 0, args.codec)
             best = ms if best is None else min(best, ms)
         assert outs == raws and consumed == [len(s) for s in streams]
         _, adler_ms = n.gpu_adler32(raws, 0, 0, True)
         _, adler_ms = n.gpu_adler32(raws, 0, 0, True)
         t0 = time.perf_counter()
         for s in packed:
-            zlib.decompress(s)
+            zlib.decompress(s, wbits)
         host_s = (time.perf_counter() - t0) * args.maps / distinct
         host = raw / host_s / 1e9
         out[kind] = {"raw_gb": round(raw / 1e9, 3), "ratio": round(raw / sum(len(s) for s in streams), 2),
-                     "device_inflate_and_adler_ms": round(best, 2), "device_gbps_raw": round(raw / best / 1e6, 2),
+                     ("device_inflate_and_crc_ms" if gz else "device_inflate_and_adler_ms"): round(best, 2), "device_gbps_raw": round(raw / best / 1e6, 2),
                      "adler_ms": round(adler_ms, 2), "adler_gbps": round(raw / adler_ms / 1e6, 1),
                      "system_zlib_1core_gbps_raw": round(host, 3), "system_zlib_x16_gbps_raw": round(host * 16, 2)}
     return out
@@ -792,7 +797,7 @@ def main() -> int:
     ap.add_argument("config", choices=["wordcount_loopback", "wordcount_tcp", "cpu_reference", "secondary_sort", "spill", "decode", "aio",
                                        "netmerger", "radix", "hybrid_budget", "combine", "combine_kernels", "checksum", "key_order"])
     ap.add_argument("--dir", default="/tmp")
-    ap.add_argument("--codec", default="snappy", choices=["snappy", "lzo", "lz4", "zlib"])
+    ap.add_argument("--codec", default="snappy", choices=["snappy", "lzo", "lz4", "zlib", "gzip"])
     ap.add_argument("--gb", type=float, default=1.0)
     ap.add_argument("--maps", type=int, default=16)
     ap.add_argument("--reducers", type=int, default=4)

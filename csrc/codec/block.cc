@@ -14,14 +14,27 @@ Codec codec_from_class(const std::string& cls, bool* unsupported) {
   if (cls.find("LzoCodec") != std::string::npos || cls.find("LzopCodec") != std::string::npos) return Codec::kLzo;
   if (cls.find("Lz4Codec") != std::string::npos) return Codec::kLz4;  // beyond the reference
   // what mapreduce.map.output.compress=true alone selects; DeflateCodec is the same codec by another name.
-  // Beyond the reference too. (GzipCodec extends DefaultCodec in Java but writes another container.)
+  // Beyond the reference too. (GzipCodec extends DefaultCodec in Java but writes another container: it is
+  // resolved by map_output_codec below and stays unsupported here, where every answer is pinned.)
   if (cls.find("DefaultCodec") != std::string::npos || cls.find("DeflateCodec") != std::string::npos) return Codec::kZlib;
   *unsupported = true;  // getCompAlg (reducer.cc:439-450) throws on anything else
   return Codec::kNone;
 }
 
+// The resolver of a job's map-output codec. codec_from_class above keeps its answers (Gzip refused: it is the
+// table of names the block and zlib entry points know), so the one codec that has entry points of its own
+// beyond that table is added here.
+Codec map_output_codec(const std::string& cls, bool* unsupported) {
+  if (cls.find("GzipCodec") != std::string::npos) {
+    *unsupported = false;
+    return Codec::kGzip;
+  }
+  return codec_from_class(cls, unsupported);
+}
+
 const char* codec_name(Codec c) {
   switch (c) {
+    case Codec::kGzip: return "gzip";
     case Codec::kSnappy: return "snappy";
     case Codec::kLzo: return "lzo1x";
     case Codec::kLz4: return "lz4";
@@ -70,6 +83,7 @@ std::vector<uint8_t> block_compress(Codec c, const uint8_t* src, size_t n, size_
 
 BlockDecoder::BlockDecoder(Codec c) : codec_(c) {
   if (c == Codec::kZlib) zlib_ = std::make_unique<Inflater>();
+  if (c == Codec::kGzip) zlib_ = std::make_unique<Inflater>(Inflater::Container::kGzip);
 }
 
 void BlockDecoder::feed(const uint8_t* p, size_t n) {

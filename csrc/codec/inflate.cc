@@ -1,10 +1,13 @@
-// Host zlib / deflate decoder (RFC 1950 / 1951) for DefaultCodec map outputs. See uda/codec.h.
+// Host zlib / deflate decoder (RFC 1950 / 1951) for DefaultCodec map outputs, and in its gzip mode (RFC 1952
+// members around the same deflate data) for GzipCodec ones. See uda/codec.h.
 //
 // One state machine serves the one-shot call and the incremental Inflater. A unit (block header, symbol
 // with its extra bits, stored chunk, trailer) is parsed from a local bit position and committed only when
 // all of its bits were there; otherwise run() returns and the unit is parsed again after the next feed.
 // Bits past the input's end read as zeros and are never acted on: every field is checked against the bits
 // that are really there before it is used, so "needs input" always wins over "corrupt".
+// A gzip member's header (with its optional fields) and its 8-byte trailer are units of the same kind: parsed
+// from the bytes that are there, committed only when whole.
 #include <algorithm>
 #include <cstring>
 
@@ -31,11 +34,84 @@ inline uint64_t peek_bits(const uint8_t* p, size_t n, uint64_t pos) {
   return w >> (pos & 7);
 }
 inline uint32_t mask(uint32_t n) { return (1u << n) - 1; }
+
+// CRC-32 (IEEE, reflected) with a table of this file's own: the stand-alone sanitizer programs build this file alone.
+struct CrcTable {
+  uint32_t t[256];
+  constexpr CrcTable() : t() {
+    for (uint32_t i = 0; i < 256; ++i) {
+      uint32_t c = i;
+      for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1)));
+      t[i] = c;
+    }
+  }
+};
+constexpr CrcTable kCrc;
+inline uint32_t crc32_update(uint32_t crc, const uint8_t* p, size_t n) {
+  uint32_t c = ~crc;
+  for (size_t i = 0; i < n; ++i) c = kCrc.t[(c ^ p[i]) & 0xFF] ^ (c >> 8);
+  return ~c;
+}
+inline uint32_t le32(const uint8_t* p) {
+  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+
+constexpr size_t kGzipMinMember = 18;  // a 10-byte header and the 8-byte trailer: no member is shorter
+// FLG bits (RFC 1952)
+constexpr uint32_t kFhcrc = 2, kFextra = 4, kFname = 8, kFcomment = 16, kFlgReserved = 0xE0;
+
+// Another member starts at p[0, n): enough bytes for the smallest header and trailer, and the magic with CM.
+inline bool gzip_member_starts(const uint8_t* p, size_t n) {
+  return n >= kGzipMinMember && p[0] == 0x1f && p[1] == 0x8b && p[2] == 8;
+}
 }  // namespace
 
-Inflater::Inflater() : buf_(kHistory + kOutBuf), lit_(inflate::kLitCap), dist_(inflate::kDistCap) {}
+Inflater::Inflater(Container c)
+    : buf_(kHistory + kOutBuf), gzip_(c == Container::kGzip), lit_(inflate::kLitCap), dist_(inflate::kDistCap) {}
 
-void Inflater::fail(const char* what) const { throw UdaError(std::string("corrupt zlib stream: ") + what); }
+void Inflater::fail(const char* what) const {
+  throw UdaError(std::string(gzip_ ? "corrupt gzip stream: " : "corrupt zlib stream: ") + what);
+}
+
+// gzip, behind a member's trailer: go on into the next member if one starts in the input that is there.
+bool Inflater::next_member() {
+  const size_t byte = (size_t)((bitpos_ + 7) >> 3);
+  if (byte > in_.size() || !gzip_member_starts(in_.data() + byte, in_.size() - byte)) return false;
+  crc_ = 0;
+  member_out_ = total_out_;
+  state_ = kHeader;
+  return true;
+}
+
+// 0 = the gzip header at p[0, n) is not whole yet; otherwise its length. Fails on what zlib refuses.
+size_t Inflater::gzip_header(const uint8_t* p, size_t n) const {
+  if (n < 10) return 0;
+  if (p[0] != 0x1f || p[1] != 0x8b) fail("incorrect header check");
+  if (p[2] != 8) fail("unknown compression method");
+  const uint32_t flg = p[3];
+  if (flg & kFlgReserved) fail("unknown header flags set");
+  size_t at = 10;  // MTIME, XFL and OS are ignored (and FTEXT)
+  if (flg & kFextra) {
+    if (n - at < 2) return 0;
+    const size_t xlen = (size_t)p[at] | ((size_t)p[at + 1] << 8);
+    at += 2;
+    if (n - at < xlen) return 0;
+    at += xlen;
+  }
+  for (const uint32_t bit : {kFname, kFcomment}) {
+    if (!(flg & bit)) continue;
+    const void* z = std::memchr(p + at, 0, n - at);
+    if (!z) return 0;
+    at = (size_t)((const uint8_t*)z - p) + 1;
+  }
+  if (flg & kFhcrc) {
+    if (n - at < 2) return 0;
+    const uint32_t stored = (uint32_t)p[at] | ((uint32_t)p[at + 1] << 8);
+    if (stored != (crc32_update(0, p, at) & 0xFFFF)) fail("header crc mismatch");
+    at += 2;
+  }
+  return at;
+}
 
 void Inflater::feed(const uint8_t* p, size_t n) {
   const size_t done = (size_t)(bitpos_ >> 3);
@@ -48,6 +124,11 @@ void Inflater::feed(const uint8_t* p, size_t n) {
 }
 
 void Inflater::sum() {
+  if (gzip_) {  // its check over the same bytes is a CRC-32
+    crc_ = crc32_update(crc_, buf_.data() + spos_, wpos_ - spos_);
+    spos_ = wpos_;
+    return;
+  }
   uint32_t a = adler_a_, b = adler_b_;
   while (spos_ < wpos_) {
     const size_t n = std::min<size_t>(5552, wpos_ - spos_);  // the most bytes before b can overflow 32 bits
@@ -80,7 +161,7 @@ size_t Inflater::read(uint8_t* dst, size_t cap) {
     got += n;
     if (rpos_ < wpos_) return got;  // cap reached with output left
     // all read: decode ahead, so finished() is current when the last bytes are handed out
-    if (state_ == kDone) return got;
+    if (state_ == kDone && !(gzip_ && next_member())) return got;
     if (wpos_ + kMaxMatch > buf_.size()) slide();
     const size_t before = wpos_;
     run();
@@ -100,6 +181,14 @@ void Inflater::run() {
     uint64_t pos = bitpos_;
     switch (state_) {
       case kHeader: {
+        if (gzip_) {  // (pos is a byte boundary: the stream's start, or the end of a member's trailer)
+          const size_t byte = (size_t)(pos >> 3);
+          const size_t len = gzip_header(in + byte, n - byte);
+          if (len == 0) return;
+          bitpos_ = pos + (uint64_t)len * 8;
+          state_ = kBlockHeader;
+          break;
+        }
         if (nbits - pos < 16) return;
         const uint64_t w = peek_bits(in, n, pos);
         if (!zlib_header_ok((uint32_t)(w & 0xFF), (uint32_t)((w >> 8) & 0xFF))) fail("bad header");
@@ -265,7 +354,7 @@ void Inflater::run() {
           }
           const uint32_t d = base + (uint32_t)((w >> used) & mask(eb));
           used += eb;
-          if ((uint64_t)d > total_out_) fail("invalid distance too far back");
+          if ((uint64_t)d > total_out_ - member_out_) fail("invalid distance too far back");
           // (the buffer holds min(total_out_, 32 KiB or more) bytes below wpos_)
           for (uint32_t i = 0; i < len; ++i) out[wpos_ + i] = out[wpos_ + i - d];
           wpos_ += len;
@@ -277,6 +366,16 @@ void Inflater::run() {
       }
       case kAdler: {
         pos = (pos + 7) & ~(uint64_t)7;
+        if (gzip_) {  // CRC-32 and ISIZE, little-endian, taken together
+          if (nbits < pos || nbits - pos < 64) return;
+          const size_t byte = (size_t)(pos >> 3);
+          sum();
+          if (le32(in + byte) != crc_) fail("incorrect data check");
+          if (le32(in + byte + 4) != (uint32_t)(total_out_ - member_out_)) fail("incorrect length check");
+          bitpos_ = pos + 64;
+          state_ = kDone;
+          break;  // (a member of no output must not read as "needs input" while another follows)
+        }
         if (nbits < pos || nbits - pos < 32) return;
         const size_t byte = (size_t)(pos >> 3);
         const uint32_t stored = ((uint32_t)in[byte] << 24) | ((uint32_t)in[byte + 1] << 16) | ((uint32_t)in[byte + 2] << 8) | in[byte + 3];
@@ -287,16 +386,18 @@ void Inflater::run() {
         return;
       }
       case kDone:
+        if (gzip_ && next_member()) break;
         return;
     }
   }
 }
 
-bool zlib_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len, size_t* consumed) {
+namespace {
+bool one_shot(Inflater::Container c, const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len, size_t* consumed) {
   *out_len = 0;
   if (consumed) *consumed = 0;
   try {
-    Inflater inf;
+    Inflater inf(c);
     inf.feed(src, n);
     size_t got = 0;
     for (size_t k; got < cap && (k = inf.read(dst + got, cap - got)) > 0;) got += k;
@@ -309,6 +410,15 @@ bool zlib_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, siz
   } catch (const UdaError&) {
     return false;
   }
+}
+}  // namespace
+
+bool zlib_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len, size_t* consumed) {
+  return one_shot(Inflater::Container::kZlib, src, n, dst, cap, out_len, consumed);
+}
+
+bool gzip_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len, size_t* consumed) {
+  return one_shot(Inflater::Container::kGzip, src, n, dst, cap, out_len, consumed);
 }
 
 }  // namespace uda

@@ -573,17 +573,17 @@ bool ReduceTask::merge_gpu_device(bool probe) {
     // (the framing walk finds the trailers; the checksum kernels go between its two passes, and the second
     // pass's synchronize brings their result)
     std::vector<int> tails;
-    // zlib (DefaultCodec): a partition is one stream with no framing, so there is nothing to walk and no
+    // zlib (DefaultCodec) and gzip (GzipCodec): a partition is one stream with no framing, so there is nothing to walk and no
     // per-round decode; the index's raw lengths lay the outputs out, and the trailers are found by the decode
     gpu::StreamPlan zplan;
     bool dev_inflate = false;
     int64_t streams = 0;
-    if (codec_ == Codec::kZlib) {
+    if (is_stream_codec(codec_)) {
       std::vector<int64_t> raws;
       for (const auto& p : parts) raws.push_back(p->raw_len);
       dev_inflate = gpu::plan_zlib_streams(cp, cl, raws, &zplan);
     }
-    const bool dev_frames = codec_ != Codec::kZlib &&
+    const bool dev_frames = !is_stream_codec(codec_) &&
                             gpu::plan_block_streams_device(codec_, cp, cl, &bp, ws.frame_scratch, ws.frame_descs, s,
                                                            &tails, launch_checksums);
     if (dev_frames) {
@@ -670,7 +670,7 @@ bool ReduceTask::merge_gpu_device(bool probe) {
       for (const auto& p : parts) ids.push_back(p->map_id);
       int bad = -1;
       std::string why;
-      ws.inflater.decode(zplan, nullptr, ws.in.as<uint8_t>(), ids, s, &tails, &bad, &why);
+      ws.inflater.decode(zplan, nullptr, ws.in.as<uint8_t>(), ids, s, &tails, &bad, &why, codec_);
       if (bad >= 0) {
         // a stream that does not decode has no known end. Where the task's other partitions carry a trailer,
         // so does this one: its CRC tells a partition damaged on its way (the checksum mismatch, as for every
@@ -698,7 +698,7 @@ bool ReduceTask::merge_gpu_device(bool probe) {
       blocks = (int64_t)bp.descs.size();
     } else {  // framing that needs a decode (multi-chunk LZO or LZ4 blocks): decode on the host
       UDA_LOG(kInfo, "device decode: %s needs a host decode (%s)",
-              codec_ == Codec::kZlib ? "a partition of unknown or 2 GiB raw length" : "framing", codec_name(codec_));
+              is_stream_codec(codec_) ? "a partition of unknown or 2 GiB raw length" : "framing", codec_name(codec_));
       std::vector<std::vector<uint8_t>> raws;
       roff.assign(1, 0);
       for (size_t i = 0; i < cp.size(); ++i) {

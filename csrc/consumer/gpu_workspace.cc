@@ -146,11 +146,11 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
       throw UdaError("compressed map output " + name_of(in_runs[i]) + " decodes to " + std::to_string(decoded) +
                      " bytes, its index says " + std::to_string(in_runs[i].raw_len));
   };
-  // zlib (DefaultCodec): no framing to walk. One inflate descriptor per run from the index's raw lengths; the
+  // zlib (DefaultCodec) and gzip (GzipCodec): no framing to walk. One inflate descriptor per run from the index's raw lengths; the
   // runs' ends, and with them their trailers, are known only once they are decoded (below, behind the copies).
   gpu::StreamPlan zplan;
   bool inflate_on_device = false;
-  if (codec == Codec::kZlib) {
+  if (is_stream_codec(codec)) {
     std::vector<int64_t> raws;
     for (const Span& sp : in_runs) raws.push_back(sp.raw_len);
     inflate_on_device = gpu::plan_zlib_streams({}, lens, raws, &zplan);
@@ -160,12 +160,12 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
     }
   }
   if (codec != Codec::kNone) {
-    decode_on_device = inflate_on_device || (codec != Codec::kZlib && gpu::plan_block_streams(codec, ptrs, lens, &plan, &tails));
+    decode_on_device = inflate_on_device || (!is_stream_codec(codec) && gpu::plan_block_streams(codec, ptrs, lens, &plan, &tails));
     if (decode_on_device && !inflate_on_device)
       for (size_t i = 0; i < ptrs.size(); ++i) check_raw_len(i, plan.raw_offset[i + 1] - plan.raw_offset[i]);
     if (!decode_on_device) {
-      if (codec == Codec::kZlib)
-        UDA_LOG(kInfo, "device decode: a zlib partition of unknown or 2 GiB raw length needs a host decode");
+      if (is_stream_codec(codec))
+        UDA_LOG(kInfo, "device decode: a %s partition of unknown or 2 GiB raw length needs a host decode", codec_name(codec));
       else
         UDA_LOG(kInfo, "device decode: framing needs a host decode (multi-chunk %s block)", codec_name(codec));
       for (size_t i = 0; i < ptrs.size(); ++i) {
@@ -265,7 +265,7 @@ DeviceMergeOut device_merge(DeviceWorkspace& ws, const std::vector<Span>& in_run
     for (const Span& sp : in_runs) ids.push_back(name_of(sp));
     int bad = -1;
     std::string why;
-    ws.inflater.decode(zplan, ws.packed.as<uint8_t>(), in.as<uint8_t>(), ids, s, &tails, &bad, &why);
+    ws.inflater.decode(zplan, ws.packed.as<uint8_t>(), in.as<uint8_t>(), ids, s, &tails, &bad, &why, codec);
     if (bad >= 0) {
       // a stream that does not decode has no known end. Where the merge's other runs carry a trailer, so does
       // this one: its CRC tells a run damaged on its way (the checksum mismatch, as for every other codec) from

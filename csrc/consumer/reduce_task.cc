@@ -302,8 +302,16 @@ int64_t MofFetcher::pull_body(uint8_t* dst, int64_t cap) {
 
 int64_t MofFetcher::pull(uint8_t* dst, int64_t cap) {
   if (!dec_) return pull_body(dst, cap);
+  // a stream the decoder refuses: the failure names the map output
+  auto read = [&](uint8_t* to, size_t room) {
+    try {
+      return dec_->read(to, room);
+    } catch (const UdaError& e) {
+      throw UdaError(std::string(e.what()) + " (map output " + p_.map_id + ")");
+    }
+  };
   for (;;) {
-    const size_t r = dec_->read(dst, (size_t)cap);
+    const size_t r = read(dst, (size_t)cap);
     if (r > 0) {
       decoded_ += (int64_t)r;
       // all but the held-back bytes are fed by the time the decoder hands out its last bytes (below): the
@@ -315,12 +323,13 @@ int64_t MofFetcher::pull(uint8_t* dst, int64_t cap) {
                          " bytes, its index says " + std::to_string(raw_len_));
         check_trailer();
       } else if (!tail_decided_ && seen_ >= part_len_ && dec_->starved()) {
-        // a zlib stream without a trailer: the held-back bytes are its own Adler-32, which the decoder has not
-        // seen. It is checked now, before the consumer sees the EOF marker in these bytes and stops reading
+        // a zlib or gzip stream without a trailer: the held-back bytes are its own check (the Adler-32; gzip: the
+        // last member's ISIZE), which the decoder has not seen. It is checked now, before the consumer sees the
+        // EOF marker in these bytes and stops reading
         tail_decided_ = true;
         dec_->feed(stored_, (size_t)stored_n_);
-        (void)dec_->read(dst + r, 0);  // (no output is left: this reads the stream's end, or throws)
-        if (!dec_->idle()) throw UdaError("compressed MOF " + p_.map_id + " ended inside its zlib stream");
+        (void)read(dst + r, 0);  // (no output is left: this reads the stream's end, or throws)
+        if (!dec_->idle()) throw UdaError("compressed MOF " + p_.map_id + " ended inside its " + codec_name(codec_) + " stream");
         if (raw_len_ > 0 && decoded_ != raw_len_)
           throw UdaError("compressed map output " + p_.map_id + " decodes to " + std::to_string(decoded_) +
                          " bytes, its index says " + std::to_string(raw_len_));
@@ -481,7 +490,7 @@ void ReduceTask::on_init(const InitParams& p_in) {
   if (kind_ == KeyKind::kUnsupported)
     throw ProtocolError("using compare function for unsupported type: " + p.key_class);
   bool unsup = false;
-  codec_ = codec_from_class(p.codec, &unsup);
+  codec_ = map_output_codec(p.codec, &unsup);
   if (unsup) throw ProtocolError("unsupported compression codec: " + p.codec);
   const int maps = p.num_maps;
   // LPQ geometry (reduce_task::init, reducer.cc:260-285)

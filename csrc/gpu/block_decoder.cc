@@ -23,7 +23,7 @@ bool plan_block_streams(Codec codec, const std::vector<const uint8_t*>& ptrs, co
   plan->descs.clear();
   plan->raw_offset.assign(1, 0);
   if (tails) tails->assign(lens.size(), 0);
-  if (codec == Codec::kZlib) return false;  // no block codec: plan_zlib_streams (stream_decoder.h)
+  if (is_stream_codec(codec)) return false;  // no block codec: plan_zlib_streams (stream_decoder.h)
   int64_t in_base = 0, raw = 0;
   for (size_t s = 0; s < lens.size(); ++s) {
     const uint8_t* p = ptrs[s];
@@ -74,7 +74,7 @@ bool plan_block_streams_device(Codec codec, const std::vector<const uint8_t*>& d
   plan->raw_offset.assign(1, 0);
   plan->raw_total = 0;
   if (tails) tails->assign((size_t)n, 0);
-  if (codec == Codec::kZlib) return false;  // no block codec: plan_zlib_streams (stream_decoder.h)
+  if (is_stream_codec(codec)) return false;  // no block codec: plan_zlib_streams (stream_decoder.h)
   if (n == 0) return true;
   // scratch: ptrs | lens | desc_first | raw_first | nblocks | raw (8 B each per stream) | status, tails (4 B)
   const size_t tb = (size_t)n * 56 + 64;

@@ -1,4 +1,7 @@
 // zlib inflate on the device: DefaultCodec map outputs, one RFC 1950 stream per partition, decoded in HBM.
+// GzipCodec map outputs too: one RFC 1952 member per partition around the same deflate data. The container is
+// uniform for a launch and is looked at twice per stream, ahead of the first block and behind the last one;
+// the block and symbol loops between do not know it.
 //
 // A zlib stream has no framing and nothing indexed inside it, so the unit of parallelism is the stream:
 // one wave64 per stream, four waves per workgroup, all streams of a reduce task in one launch (a lane per
@@ -22,9 +25,18 @@
 // access); every loop iteration consumes at least one input bit or ends with a status, and bits past the
 // input's end are zeros that are never acted on (a field is checked against the bits really there first), so
 // a corrupt or truncated stream ends with status != 0: it never spins and never faults.
-// The stream's Adler-32 is read, not verified, here: adler32.hip sums the decoded bytes right behind this
-// launch and the host compares (block_decoder's sibling stream_decoder.cc).
+// The gzip header is walked bytewise ahead of the bit reader under the same contract: every step checks
+// ip < ip_end before its read and takes at least one byte or ends with a status, so a header field that never
+// terminates cannot spin and no byte at or past src + src_len is read; its optional FHCRC is verified in the
+// same walk by a bitwise CRC-32 without a table. Only one member is decoded: what lies behind its trailer is
+// the host's to judge (stream_decoder.cc).
+// The stream's own check (zlib: Adler-32; gzip: CRC-32, with ISIZE) is read, not verified, here: adler32.hip /
+// crc32.hip sum the decoded bytes right behind this launch and the host compares (block_decoder's sibling
+// stream_decoder.cc).
 #include <hip/hip_runtime.h>
+
+#include <stdexcept>
+#include <string>
 
 #include "codec/inflate_tables.h"
 #include "kernels.h"
@@ -267,11 +279,68 @@ __device__ __forceinline__ int huffman_block(Stream& s, const WaveLds& L) {
   }
 }
 
-__device__ __forceinline__ int inflate_stream(Stream& s, WaveLds& L, uint32_t* adler) {
-  refill(s);
-  if (s.bc < 16) return kInflateTruncated;
-  if (!zlib_header_ok((uint32_t)(s.bb & 0xFF), (uint32_t)((s.bb >> 8) & 0xFF))) return kInflateCorrupt;
-  consume(s, 16);
+// One header byte at s.ip into *b and into the header's CRC-32 (bitwise, no table); false at the input's end.
+__device__ __forceinline__ bool header_byte(Stream& s, uint32_t* b, uint32_t& crc) {
+  if (s.ip >= s.ip_end) return false;
+  const uint32_t v = uni(s.ib[s.ip]);
+  ++s.ip;
+  crc ^= v;
+  for (int k = 0; k < 8; ++k) crc = (crc >> 1) ^ (0xEDB88320u & (0u - (crc & 1)));
+  *b = v;
+  return true;
+}
+
+// The gzip member header (RFC 1952) from s.ip = 0, bytewise and before the bit reader starts: on kInflateOk
+// s.ip is the first deflate byte. Every step checks s.ip < s.ip_end ahead of its read and takes at least one
+// byte or returns, so a field that never ends (an FNAME without its zero, an XLEN past the input) ends with
+// kInflateTruncated at the input's end. MTIME, XFL, OS and FTEXT are ignored, as zlib ignores them.
+__device__ __forceinline__ int gzip_header(Stream& s) {
+  uint32_t crc = 0xFFFFFFFFu, b = 0, flg = 0;
+  for (int i = 0; i < 10; ++i) {
+    if (!header_byte(s, &b, crc)) return kInflateTruncated;
+    if ((i == 0 && b != 0x1f) || (i == 1 && b != 0x8b) || (i == 2 && b != 8)) return kInflateCorrupt;
+    if (i == 3) {
+      flg = b;
+      if (flg & 0xE0) return kInflateCorrupt;  // reserved bits
+    }
+  }
+  if (flg & 4) {  // FEXTRA: u16 XLEN, little-endian, and that many bytes
+    uint32_t lo, hi;
+    if (!header_byte(s, &lo, crc) || !header_byte(s, &hi, crc)) return kInflateTruncated;
+    const uint32_t xlen = lo | (hi << 8);
+    if (xlen > s.ip_end - s.ip) return kInflateTruncated;
+    if (flg & 2) {  // only a header CRC needs the bytes themselves
+      for (uint32_t k = 0; k < xlen; ++k)
+        if (!header_byte(s, &b, crc)) return kInflateTruncated;
+    } else {
+      s.ip += xlen;
+    }
+  }
+  for (uint32_t bit = 8; bit <= 16; bit <<= 1) {  // FNAME, FCOMMENT: zero-terminated
+    if (!(flg & bit)) continue;
+    do {
+      if (!header_byte(s, &b, crc)) return kInflateTruncated;
+    } while (b != 0);
+  }
+  if (flg & 2) {  // FHCRC: the low 16 bits of the CRC-32 of the header bytes before it
+    const uint32_t want = ~crc & 0xFFFF;
+    uint32_t lo, hi;
+    if (!header_byte(s, &lo, crc) || !header_byte(s, &hi, crc)) return kInflateTruncated;
+    if ((lo | (hi << 8)) != want) return kInflateCorrupt;
+  }
+  return kInflateOk;
+}
+
+__device__ __forceinline__ int inflate_stream(Stream& s, WaveLds& L, int container, uint32_t* check, uint32_t* isize) {
+  if (container == kContainerGzip) {
+    const int st = gzip_header(s);
+    if (st) return st;
+  } else {
+    refill(s);
+    if (s.bc < 16) return kInflateTruncated;
+    if (!zlib_header_ok((uint32_t)(s.bb & 0xFF), (uint32_t)((s.bb >> 8) & 0xFF))) return kInflateCorrupt;
+    consume(s, 16);
+  }
   for (;;) {
     refill(s);
     if (s.bc < 3) return kInflateTruncated;
@@ -308,15 +377,22 @@ __device__ __forceinline__ int inflate_stream(Stream& s, WaveLds& L, uint32_t* a
     if (last) break;
   }
   to_bytes(s);
-  if (s.ip_end - s.ip < 4) return kInflateTruncated;
   const uint8_t* p = s.ib + s.ip;
-  *adler = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+  if (container == kContainerGzip) {  // CRC-32 and ISIZE, little-endian
+    if (s.ip_end - s.ip < 8) return kInflateTruncated;
+    *check = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+    *isize = (uint32_t)p[4] | ((uint32_t)p[5] << 8) | ((uint32_t)p[6] << 16) | ((uint32_t)p[7] << 24);
+    s.ip += 8;
+    return kInflateOk;
+  }
+  if (s.ip_end - s.ip < 4) return kInflateTruncated;
+  *check = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
   s.ip += 4;
   return kInflateOk;
 }
 
 __global__ void __launch_bounds__(64 * kWavesPerBlock)
-inflate_kernel(const uint8_t* in, uint8_t* out, const InflateDesc* descs, int n, InflateResult* results) {
+inflate_kernel(const uint8_t* in, uint8_t* out, const InflateDesc* descs, int n, InflateResult* results, int container) {
   __shared__ WaveLds lds[kWavesPerBlock];
   const int wave = (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
   const int idx = (int)blockIdx.x * kWavesPerBlock + wave;
@@ -333,7 +409,7 @@ inflate_kernel(const uint8_t* in, uint8_t* out, const InflateDesc* descs, int n,
   s.lit = 0;
   s.flushed = 0;
   s.lane = lane;
-  uint32_t adler = 0;
+  uint32_t check = 0, isize = 0;
   int status;
   constexpr int64_t kLimit = 1ll << 31;
   if (d.src_len < 0 || d.src_len >= kLimit || d.raw_len < 0 || d.raw_len >= kLimit) {
@@ -342,24 +418,28 @@ inflate_kernel(const uint8_t* in, uint8_t* out, const InflateDesc* descs, int n,
   } else {
     s.ip_end = (uint32_t)d.src_len;
     s.op_end = (uint32_t)d.raw_len;
-    status = inflate_stream(s, lds[wave], &adler);
+    status = inflate_stream(s, lds[wave], container, &check, &isize);
   }
   if (lane == 0) {
     InflateResult r;
     r.consumed = (int64_t)s.ip;
     r.produced = (int64_t)s.op;
-    r.adler_stored = adler;
+    r.check_stored = check;
     r.status = status;
+    r.isize = isize;
     results[idx] = r;
   }
 }
 
 }  // namespace
 
-void launch_inflate_streams(const uint8_t* in, uint8_t* out, const InflateDesc* d, int n, InflateResult* r, hipStream_t s) {
+void launch_inflate_streams(const uint8_t* in, uint8_t* out, const InflateDesc* d, int n, InflateResult* r, hipStream_t s,
+                            int container) {
   if (n <= 0) return;
+  if (container != kContainerZlib && container != kContainerGzip)
+    throw std::invalid_argument("launch_inflate_streams: unknown container " + std::to_string(container));
   const int blocks = (n + kWavesPerBlock - 1) / kWavesPerBlock;
-  hipLaunchKernelGGL(inflate_kernel, dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), 0, s, in, out, d, n, r);
+  hipLaunchKernelGGL(inflate_kernel, dim3((unsigned)blocks), dim3(64 * kWavesPerBlock), 0, s, in, out, d, n, r, container);
 }
 
 InflateGeometry inflate_geometry() {

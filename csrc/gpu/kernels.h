@@ -345,21 +345,27 @@ void launch_frame_streams(const uint8_t* const* ptrs, const int64_t* lens, int n
                           const int64_t* desc_first, const int64_t* raw_first, int64_t* nblocks, int64_t* raw,
                           DecodeDesc* out, int* status, hipStream_t s, int* tails = nullptr);
 
-// ---------------------------------------------------------------- zlib inflate (DefaultCodec), inflate.hip
-// One zlib stream (RFC 1950: a partition as DefaultCodec's CompressorStream wrote it) per descriptor, decoded
-// by one wave64. src is an offset into `in`, or an absolute address when in == nullptr (as DecodeDesc); dst is
-// an offset into `out`. At most raw_len bytes are written at dst and no byte at or past src + src_len is read.
-// Streams and outputs are below 2 GiB each (status kInflateTooBig otherwise: decode those on the host).
+// ---------------------------------------------------------------- zlib / gzip inflate, inflate.hip
+// One deflate stream in its container per descriptor, decoded by one wave64: a zlib stream (RFC 1950: a
+// partition as DefaultCodec's CompressorStream wrote it) or one gzip member (RFC 1952: GzipCodec), the
+// container uniform for the launch. src is an offset into `in`, or an absolute address when in == nullptr (as
+// DecodeDesc); dst is an offset into `out`. At most raw_len bytes are written at dst and no byte at or past
+// src + src_len is read. Streams and outputs are below 2 GiB each (status kInflateTooBig otherwise: decode
+// those on the host).
 struct InflateDesc {
   int64_t src, src_len, dst, raw_len;
 };
-// consumed: bytes of src the stream took, header to Adler-32; produced: bytes written; adler_stored: the
-// stream's own Adler-32 (not verified here: launch_adler32 over the output, compared on the host).
-// status 0 = the stream ended after BFINAL with its Adler-32 read; produced may still differ from raw_len.
+// consumed: bytes of src the stream took, header to trailer (zlib: its Adler-32; gzip: the member's CRC-32 and
+// ISIZE; bytes behind one gzip member, a second member among them, are left to the host); produced: bytes
+// written; check_stored: the container's own check of the decoded bytes as the stream stores it, Adler-32 or
+// CRC-32 (not verified here: launch_adler32 / launch_crc32 over the output, compared on the host); isize: the
+// gzip member's stored length mod 2^32 (zlib: 0).
+// status 0 = the stream ended after BFINAL with its trailer read; produced may still differ from raw_len.
 struct InflateResult {
   int64_t consumed, produced;
-  uint32_t adler_stored;
+  uint32_t check_stored;
   int status;
+  uint32_t isize;
 };
 enum InflateStatus : int {
   kInflateOk = 0,
@@ -368,7 +374,9 @@ enum InflateStatus : int {
   kInflateOverflow = 3,   // more output than raw_len
   kInflateTooBig = 4,
 };
-void launch_inflate_streams(const uint8_t* in, uint8_t* out, const InflateDesc* d, int n, InflateResult* r, hipStream_t s);
+enum InflateContainer : int { kContainerZlib = 0, kContainerGzip = 1 };
+void launch_inflate_streams(const uint8_t* in, uint8_t* out, const InflateDesc* d, int n, InflateResult* r, hipStream_t s,
+                            int container = kContainerZlib);
 // Constants of the kernel for tests that lay codes on its boundaries: the register input window and the
 // alignment of its base, the literals staged in registers before one store, waves (streams) per workgroup,
 // LDS bytes per wave.

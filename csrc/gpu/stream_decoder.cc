@@ -1,4 +1,4 @@
-// zlib stream plan and device decode: see stream_decoder.h.
+// zlib / gzip stream plan and device decode: see stream_decoder.h.
 #include "stream_decoder.h"
 
 #include <cstdio>
@@ -44,18 +44,33 @@ size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 void DeviceStreamDecoder::decode(const StreamPlan& plan, const uint8_t* d_in, uint8_t* d_out,
                                  const std::vector<std::string>& ids, hipStream_t s, std::vector<int>* tails,
-                                 int* failed, std::string* why) {
+                                 int* failed, std::string* why, Codec container) {
+  if (!is_stream_codec(container)) throw UdaError("DeviceStreamDecoder: " + std::string(codec_name(container)) + " is no stream codec");
+  const bool gzip = container == Codec::kGzip;
   const int n = (int)plan.descs.size();
   if (failed) *failed = -1;
   if (tails) tails->assign((size_t)n, 0);
   results_.assign((size_t)n, InflateResult{});
   if (n == 0) return;
   trace::Range tr("uda.inflate_streams");
-  // scratch: descs | results | out ptrs | out lens | adler out | adler work
+  // scratch: descs | results | out ptrs | out lens | check out | adler work; gzip, in place of the last:
+  // crc descs | chunk_first | crc chunk states
   const size_t o_desc = 0, o_res = up16(o_desc + (size_t)n * sizeof(InflateDesc));
   const size_t o_ptr = up16(o_res + (size_t)n * sizeof(InflateResult)), o_len = o_ptr + (size_t)n * 8;
   const size_t o_adler = up16(o_len + (size_t)n * 8), o_work = up16(o_adler + (size_t)n * 4);
-  const size_t bytes = o_work + (size_t)n * 16;
+  std::vector<CrcDesc> cdesc;
+  std::vector<int64_t> cfirst;
+  int64_t chunks = 0;
+  const size_t o_first = up16(o_work + (size_t)n * sizeof(CrcDesc));
+  size_t o_states = 0, bytes = o_work + (size_t)n * 16;
+  if (gzip) {  // the output addresses and raw lengths are known here, so is the CRC kernel's chunk plan
+    cdesc.resize((size_t)n);
+    cfirst.resize((size_t)n + 1);
+    for (int i = 0; i < n; ++i) cdesc[(size_t)i] = CrcDesc{d_out + plan.descs[(size_t)i].dst, plan.descs[(size_t)i].raw_len};
+    chunks = crc32_chunk_plan(cdesc.data(), n, cfirst.data());
+    o_states = up16(o_first + ((size_t)n + 1) * 8);
+    bytes = o_states + crc32_ws_bytes(chunks);
+  }
   if (scratch_.size() < bytes) scratch_.alloc(bytes + bytes / 2);
   uint8_t* const base = scratch_.as<uint8_t>();
   std::vector<const uint8_t*> optr((size_t)n);
@@ -68,12 +83,20 @@ void DeviceStreamDecoder::decode(const StreamPlan& plan, const uint8_t* d_in, ui
   HIP_CHECK(hipMemcpyAsync(base + o_ptr, optr.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(base + o_len, olen.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemsetAsync(base + o_res, 0xFF, (size_t)n * sizeof(InflateResult), s));  // (a status no wave wrote reads as an error)
+  if (gzip) {
+    HIP_CHECK(hipMemcpyAsync(base + o_work, cdesc.data(), (size_t)n * sizeof(CrcDesc), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(base + o_first, cfirst.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
+  }
   launch_inflate_streams(d_in, d_out, reinterpret_cast<const InflateDesc*>(base + o_desc), n,
-                         reinterpret_cast<InflateResult*>(base + o_res), s);
+                         reinterpret_cast<InflateResult*>(base + o_res), s, gzip ? kContainerGzip : kContainerZlib);
   HIP_CHECK(hipGetLastError());
   // the format's own integrity check, always on: over the bytes just decoded, in the same pass over s
-  launch_adler32(reinterpret_cast<const uint8_t* const*>(base + o_ptr), reinterpret_cast<const int64_t*>(base + o_len), n,
-                 reinterpret_cast<uint32_t*>(base + o_adler), reinterpret_cast<uint64_t*>(base + o_work), s);
+  if (gzip)
+    launch_crc32(reinterpret_cast<const CrcDesc*>(base + o_work), n, reinterpret_cast<const int64_t*>(base + o_first), chunks,
+                 base + o_states, reinterpret_cast<uint32_t*>(base + o_adler), s);
+  else
+    launch_adler32(reinterpret_cast<const uint8_t* const*>(base + o_ptr), reinterpret_cast<const int64_t*>(base + o_len), n,
+                   reinterpret_cast<uint32_t*>(base + o_adler), reinterpret_cast<uint64_t*>(base + o_work), s);
   HIP_CHECK(hipGetLastError());
   std::vector<uint32_t> adler((size_t)n);
   HIP_CHECK(hipMemcpyAsync(results_.data(), base + o_res, (size_t)n * sizeof(InflateResult), hipMemcpyDeviceToHost, s));
@@ -84,18 +107,34 @@ void DeviceStreamDecoder::decode(const StreamPlan& plan, const uint8_t* d_in, ui
     const InflateDesc& d = plan.descs[(size_t)i];
     const std::string id = (size_t)i < ids.size() ? ids[(size_t)i] : "#" + std::to_string(i);
     if (r.status != kInflateOk)
-      return "corrupt zlib stream in map output " + id + " (" + status_text(r.status) + ", device inflate)";
+      return std::string(gzip ? "corrupt gzip stream in map output " : "corrupt zlib stream in map output ") + id + " (" +
+             status_text(r.status) + ", device inflate)";
+    const int64_t tail = d.src_len - r.consumed;
+    if (gzip && tail >= 18) {
+      // what the host decoders take for the start of another member (Inflater::next_member). Asked first: the
+      // index's raw length covers every member, so the length and CRC comparisons below (over raw_len bytes)
+      // would only say that one member decodes to less. The three bytes are read from where the stream lies:
+      // the device input, or the absolute address the descriptor holds
+      uint8_t head[3] = {0, 0, 0};
+      const uint8_t* at = (d_in ? d_in + d.src : reinterpret_cast<const uint8_t*>((uintptr_t)d.src)) + r.consumed;
+      HIP_CHECK(hipMemcpy(head, at, sizeof head, hipMemcpyDefault));
+      if (head[0] == 0x1f && head[1] == 0x8b && head[2] == 8)
+        return "gzip map output " + id + " holds more than one member (the device inflate decodes one; "
+               "mapred.uda.gpu.decompress=0 decodes it on the host)";
+    }
     if (r.produced != d.raw_len)
       return "compressed map output " + id + " decodes to " + std::to_string(r.produced) + " bytes, its index says " +
              std::to_string(d.raw_len);
-    if (r.adler_stored != adler[(size_t)i]) {
+    if (r.check_stored != adler[(size_t)i]) {
       char buf[64];
-      std::snprintf(buf, sizeof buf, "stored 0x%08x, computed 0x%08x", r.adler_stored, adler[(size_t)i]);
-      return "zlib Adler-32 mismatch in map output " + id + ": " + buf;
+      std::snprintf(buf, sizeof buf, "stored 0x%08x, computed 0x%08x", r.check_stored, adler[(size_t)i]);
+      return std::string(gzip ? "gzip CRC-32 mismatch in map output " : "zlib Adler-32 mismatch in map output ") + id + ": " + buf;
     }
-    const int64_t tail = d.src_len - r.consumed;
+    if (gzip && r.isize != (uint32_t)r.produced)
+      return "gzip length mismatch in map output " + id + ": stored " + std::to_string(r.isize) + ", decoded " +
+             std::to_string(r.produced);
     if (tail != 0 && tail != kIFileChecksumBytes)
-      return "corrupt zlib stream in map output " + id + ": " + std::to_string(tail) +
+      return std::string(gzip ? "corrupt gzip stream in map output " : "corrupt zlib stream in map output ") + id + ": " + std::to_string(tail) +
              " bytes behind its end (an IFile checksum has " + std::to_string(kIFileChecksumBytes) + ")";
     if (tails) (*tails)[(size_t)i] = (int)tail;
     return std::string();

@@ -1,5 +1,5 @@
-// Host side of the zlib (DefaultCodec) device decode: one inflate descriptor per partition and the launches
-// of csrc/gpu/inflate.hip and adler32.hip. The sibling of block_decoder.h for the codec that has no blocks:
+// Host side of the zlib (DefaultCodec) and gzip (GzipCodec) device decode: one inflate descriptor per partition and the launches
+// of csrc/gpu/inflate.hip and adler32.hip (gzip: crc32.hip). The sibling of block_decoder.h for the codec that has no blocks:
 // a partition is one zlib stream, its raw size comes from the index and its end (and with it whether an IFile
 // checksum trailer follows) is known only once it has been decoded.
 #pragma once
@@ -11,6 +11,7 @@
 
 #include "device_engine.h"
 #include "kernels.h"
+#include "uda/codec.h"
 
 namespace uda {
 namespace gpu {
@@ -36,12 +37,21 @@ class DeviceStreamDecoder {
   // included, the reason in brackets), "compressed map output <id> decodes to N bytes, its index says M",
   // "zlib Adler-32 mismatch in map output <id>: stored 0x..., computed 0x...", and a malformed tail.
   // tails[i] = bytes of stream i behind its Adler-32: 0, or 4 (an IFile checksum trailer).
+  // container = Codec::kGzip: the streams are gzip members. The launch decodes them in gzip mode and the
+  // batched CRC-32 (launch_crc32, its descriptors and chunk plan laid from the host-known output addresses
+  // and raw lengths, its workspace from this decoder's scratch) takes the Adler-32's place on the same
+  // stream. Errors: "corrupt gzip stream in map output <id> (<reason>, device inflate)", "gzip CRC-32
+  // mismatch in map output <id>: stored 0x..., computed 0x...", "gzip length mismatch in map output <id>:
+  // stored N, decoded M" (ISIZE against the bytes produced mod 2^32), and, the device inflate decoding one
+  // member per stream, "gzip map output <id> holds more than one member (...)" when the bytes behind a good
+  // member are neither 0 nor 4 and are 18 or more starting 1f 8b 08. The zlib messages are unchanged.
   // failed (optional): instead of throwing, the first stream in error is reported there with its message in
   // *why (-1: none) and the other streams' tails are still filled in. A stream that does not decode has no
   // known end, so the caller that verifies IFile checksums can first hold that partition's bytes against the
   // trailer its neighbours show it to have, and report a partition damaged on its way as a checksum mismatch.
   void decode(const StreamPlan& plan, const uint8_t* d_in, uint8_t* d_out, const std::vector<std::string>& ids,
-              hipStream_t s, std::vector<int>* tails, int* failed = nullptr, std::string* why = nullptr);
+              hipStream_t s, std::vector<int>* tails, int* failed = nullptr, std::string* why = nullptr,
+              Codec container = Codec::kZlib);
   const std::vector<InflateResult>& results() const { return results_; }
 
  private:

@@ -836,6 +836,13 @@ PYBIND11_MODULE(_uda_native, m) {
     int v = (int)codec_from_class(c, &unsup);
     return unsup ? -1 : v;
   });
+  // The codec of a job's map outputs, as INIT resolves it: codec_from_class's answers plus GzipCodec -> 5
+  // (codec_from_class itself keeps refusing Gzip: see uda/codec.h). -1 = unsupported.
+  m.def("map_output_codec", [](const std::string& c) {
+    bool unsup = false;
+    int v = (int)map_output_codec(c, &unsup);
+    return unsup ? -1 : v;
+  });
   m.def("block_compress", [](int codec, py::bytes b, size_t block) {
     std::string s = b;
     auto v = block_compress((Codec)codec, (const uint8_t*)s.data(), s.size(), block);
@@ -866,6 +873,18 @@ PYBIND11_MODULE(_uda_native, m) {
     size_t n = 0, used = 0;
     if (!zlib_decompress((const uint8_t*)s.data(), s.size(), (uint8_t*)&out[0], cap, &n, &used))
       throw py::value_error("corrupt zlib data");
+    out.resize(n);
+    return py::make_tuple(py::bytes(out), used);
+  }, py::arg("data"), py::arg("cap"));
+  // gzip (GzipCodec) one-shot host decode of one or more concatenated members: (raw bytes, bytes of the input
+  // the members took). ValueError for anything zlib's inflate with wbits = 31 refuses, anything truncated, a
+  // CRC-32 or ISIZE mismatch or more than cap bytes of output.
+  m.def("gzip_decompress", [](py::bytes b, size_t cap) {
+    std::string s = b;
+    std::string out(cap, '\0');
+    size_t n = 0, used = 0;
+    if (!gzip_decompress((const uint8_t*)s.data(), s.size(), (uint8_t*)&out[0], cap, &n, &used))
+      throw py::value_error("corrupt gzip data");
     out.resize(n);
     return py::make_tuple(py::bytes(out), used);
   }, py::arg("data"), py::arg("cap"));
@@ -2557,8 +2576,12 @@ PYBIND11_MODULE(_uda_native, m) {
   // zlib streams inflated on the device in one launch (gpu/stream_decoder.h): (raw streams, bytes each stream
   // took, ms). Output i is raw_lens[i] bytes followed by 256 guard bytes of 0xA5, the whole buffer 0xA5 before
   // the launch; a guard byte that changed is an error here whatever the decode said.
-  m.def("gpu_inflate_streams", [](const std::vector<std::string>& streams, const std::vector<int64_t>& raw_lens, int device) {
+  // container: "zlib" (default) or "gzip", one gzip member per stream.
+  m.def("gpu_inflate_streams", [](const std::vector<std::string>& streams, const std::vector<int64_t>& raw_lens, int device,
+                                  const std::string& container) {
     if (streams.size() != raw_lens.size()) throw py::value_error("one raw length per stream");
+    if (container != "zlib" && container != "gzip") throw py::value_error("container: zlib or gzip");
+    const Codec cont = container == "gzip" ? Codec::kGzip : Codec::kZlib;
     constexpr int64_t kGuard = 256;
     std::vector<std::string> outs;
     std::vector<int64_t> consumed;
@@ -2590,7 +2613,7 @@ PYBIND11_MODULE(_uda_native, m) {
       std::string err;
       auto t0 = std::chrono::steady_clock::now();
       try {
-        dec.decode(plan, din.as<uint8_t>(), dout.as<uint8_t>(), {}, s, nullptr);
+        dec.decode(plan, din.as<uint8_t>(), dout.as<uint8_t>(), {}, s, nullptr, nullptr, nullptr, cont);
       } catch (const UdaError& e) {
         err = e.what();
       }
@@ -2615,7 +2638,7 @@ PYBIND11_MODULE(_uda_native, m) {
     py::list l;
     for (auto& o : outs) l.append(py::bytes(o));
     return py::make_tuple(py::object(l), consumed, ms);
-  }, py::arg("streams"), py::arg("raw_lens"), py::arg("device") = 0);
+  }, py::arg("streams"), py::arg("raw_lens"), py::arg("device") = 0, py::arg("container") = "zlib");
   // zlib.adler32 of every item in one batched launch (gpu/adler32.hip); item i starts `misalign` bytes past a
   // 16-byte boundary of the device buffer.
   // timed: returns (values, ms of the launch alone, from its queueing to its result) instead.

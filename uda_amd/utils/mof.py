@@ -1,26 +1,29 @@
 """Map-output files (MOFs) in Hadoop's on-disk layout, for tests, tools and the loopback configs.
 
 file.out holds one IFile partition per reducer back to back (optionally block-compressed, or with
-codec "zlib" each partition one zlib stream with no framing, as DefaultCodec's CompressorStream writes it);
+codec "zlib" each partition one zlib stream with no framing, as DefaultCodec's CompressorStream writes it, or
+with codec "gzip" one gzip member, as GzipCodec's does);
 file.out.index holds, per partition, three big-endian longs {startOffset, rawLength, partLength}
 followed by a CRC32 of those bytes as a big-endian long (Hadoop SpillRecord). The index record is
 the tuple the provider's getPathUda callback returns (IndexRecordBridge.java:26-34).
 """
 from __future__ import annotations
 
+import gzip
 import os
 import struct
 import zlib
 
 from .._native import native
 
-CODECS = {None: 0, "snappy": 1, "lzo": 2, "lz4": 3, "zlib": 4}
+CODECS = {None: 0, "snappy": 1, "lzo": 2, "lz4": 3, "zlib": 4, "gzip": 5}
 CODEC_CLASSES = {
     None: None,
     "snappy": "org.apache.hadoop.io.compress.SnappyCodec",
     "lzo": "com.hadoop.compression.lzo.LzoCodec",
     "lz4": "org.apache.hadoop.io.compress.Lz4Codec",
     "zlib": "org.apache.hadoop.io.compress.DefaultCodec",
+    "gzip": "org.apache.hadoop.io.compress.GzipCodec",
 }
 
 
@@ -36,6 +39,8 @@ def encode_partitions(partitions: list[bytes], codec: str | None = None, block_s
         raw = len(p)
         if codec == "zlib":  # no block framing: the partition is a single stream (block_size plays no part)
             body = zlib.compress(p)
+        elif codec == "gzip":  # one member with the bare header, what Hadoop's writers emit
+            body = gzip.compress(p, mtime=0)
         else:
             body = native().block_compress(CODECS[codec], p, block_size) if codec else p
         if checksum:
