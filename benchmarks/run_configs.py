@@ -9,7 +9,8 @@
   secondary_sort      variable-length Text keys with long common prefixes + partition skew: GPU generic
                       merge (F1/F2/F3/F4 kernels) vs the CPU heap merge on the same runs.
   decode              F6 Snappy / LZO1X block decode on the device vs the host decoder; --codec zlib / gzip: the
-                      device inflate (one wave per stream, --maps streams) vs the system zlib.
+                      device inflate (one wave per stream, --maps streams) vs the system zlib; --codec zstd: the
+                      device zstd decode (one wave per frame) vs libzstd on 16 threads where it loads.
   netmerger           secondary-sort data through provider -> NetMerger -> dataFromUda: CPU heap merge vs
                       GPU backend (online and hybrid LPQ/RPQ).
   aio                 AsyncIO (io_uring / thread pool, O_DIRECT) read bandwidth vs sequential pread.
@@ -190,6 +191,8 @@ def decode(args) -> dict:
     n = native()
     if args.codec in ("zlib", "gzip"):
         return decode_zlib(args, n)
+    if args.codec == "zstd":
+        return decode_zstd(args, n)
     codec = {"snappy": 1, "lzo": 2, "lz4": 3}[args.codec]
     rows = int(args.gb * 1e9 / 100 / args.maps)
     runs = [m[0] for m in n.generate_runs("secondary", args.maps, 1, rows, 5)]
@@ -248,6 +251,65 @@ def decode_zlib(args, n) -> dict:
                      ("device_inflate_and_crc_ms" if gz else "device_inflate_and_adler_ms"): round(best, 2), "device_gbps_raw": round(raw / best / 1e6, 2),
                      "adler_ms": round(adler_ms, 2), "adler_gbps": round(raw / adler_ms / 1e6, 1),
                      "system_zlib_1core_gbps_raw": round(host, 3), "system_zlib_x16_gbps_raw": round(host * 16, 2)}
+    return out
+
+
+def decode_zstd(args, n) -> dict:
+    """Device zstd decode of ZStandardCodec partitions, one wave per frame: the launch's raw GB/s for --maps frames of
+    TeraSort and of wordcount partitions of --gb in all. Where libzstd.so.1 loads, the frames are what it writes at
+    level 3 (Hadoop's default: Huffman literals, described tables) and the yardstick is its ZSTD_decompress over
+    the same frames on 16 threads (ctypes calls release the GIL); otherwise the frames come from the in-tree
+    encoder (Raw literals, Predefined tables) and the yardstick is the in-tree host decoder on one core."""
+    import ctypes
+    from concurrent.futures import ThreadPoolExecutor
+    try:
+        lib = ctypes.CDLL("libzstd.so.1")
+        for f in ("ZSTD_compressBound", "ZSTD_compress", "ZSTD_decompress"):
+            getattr(lib, f).restype = ctypes.c_size_t
+    except OSError:
+        lib = None
+
+    def lib_compress(raw):
+        cap = lib.ZSTD_compressBound(ctypes.c_size_t(len(raw)))
+        buf = ctypes.create_string_buffer(cap)
+        r = lib.ZSTD_compress(buf, ctypes.c_size_t(cap), raw, ctypes.c_size_t(len(raw)), 3)
+        return buf.raw[:r]
+
+    out = {"config": f"device zstd decode, {args.maps} frames, one wave per frame", "streams": args.maps,
+           "frames_by": "libzstd level 3" if lib else "in-tree encoder"}
+    rows = max(1, int(args.gb * 1e9 / 100 / args.maps))
+    distinct = min(args.maps, 32)  # (the frames repeat these partitions: the generator is the slow part)
+    for kind in ("terasort", "wordcount"):
+        parts = [m[0] for m in n.generate_runs(kind, distinct, 1, rows, 5)]
+        raws = [parts[i % distinct] for i in range(args.maps)]
+        packed = [lib_compress(p) if lib else n.zstd_compress(p) for p in parts]
+        streams = [packed[i % distinct] for i in range(args.maps)]
+        raw = sum(len(r) for r in raws)
+        n.gpu_zstd_streams(streams[:1], [len(raws[0])])  # warm up
+        best = None
+        for _ in range(3):
+            outs, consumed, _, ms, _ = n.gpu_zstd_streams(streams, [len(r) for r in raws])
+            best = ms if best is None else min(best, ms)
+        assert outs == raws and consumed == [len(s) for s in streams]
+        res = {"raw_gb": round(raw / 1e9, 3), "ratio": round(raw / sum(len(s) for s in streams), 2),
+               "device_decode_ms": round(best, 2), "device_gbps_raw": round(raw / best / 1e6, 2)}
+        if lib:
+            bufs = [ctypes.create_string_buffer(max(len(r), 1)) for r in raws[:16]]
+
+            def one(i):
+                for k in range(i, len(streams), 16):
+                    lib.ZSTD_decompress(bufs[i], ctypes.c_size_t(len(raws[k])), streams[k], ctypes.c_size_t(len(streams[k])))
+
+            t0 = time.perf_counter()
+            with ThreadPoolExecutor(16) as ex:
+                list(ex.map(one, range(min(16, len(streams)))))
+            res["libzstd_16_threads_gbps_raw"] = round(raw / (time.perf_counter() - t0) / 1e9, 2)
+        else:
+            t0 = time.perf_counter()
+            for s, p in zip(packed, parts):
+                n.zstd_decompress(s, len(p))
+            res["host_decoder_1core_gbps_raw"] = round(raw / ((time.perf_counter() - t0) * args.maps / distinct) / 1e9, 3)
+        out[kind] = res
     return out
 
 
@@ -797,7 +859,7 @@ def main() -> int:
     ap.add_argument("config", choices=["wordcount_loopback", "wordcount_tcp", "cpu_reference", "secondary_sort", "spill", "decode", "aio",
                                        "netmerger", "radix", "hybrid_budget", "combine", "combine_kernels", "checksum", "key_order"])
     ap.add_argument("--dir", default="/tmp")
-    ap.add_argument("--codec", default="snappy", choices=["snappy", "lzo", "lz4", "zlib", "gzip"])
+    ap.add_argument("--codec", default="snappy", choices=["snappy", "lzo", "lz4", "zlib", "gzip", "zstd"])
     ap.add_argument("--gb", type=float, default=1.0)
     ap.add_argument("--maps", type=int, default=16)
     ap.add_argument("--reducers", type=int, default=4)

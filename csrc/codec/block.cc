@@ -32,8 +32,18 @@ Codec map_output_codec(const std::string& cls, bool* unsupported) {
   return codec_from_class(cls, unsupported);
 }
 
+// ZStandardCodec on top of map_output_codec, whose answers are pinned in turn (see uda/codec.h).
+Codec job_codec(const std::string& cls, bool* unsupported) {
+  if (cls.find("ZStandardCodec") != std::string::npos) {
+    *unsupported = false;
+    return Codec::kZstd;
+  }
+  return map_output_codec(cls, unsupported);
+}
+
 const char* codec_name(Codec c) {
   switch (c) {
+    case Codec::kZstd: return "zstd";
     case Codec::kGzip: return "gzip";
     case Codec::kSnappy: return "snappy";
     case Codec::kLzo: return "lzo1x";
@@ -84,10 +94,12 @@ std::vector<uint8_t> block_compress(Codec c, const uint8_t* src, size_t n, size_
 BlockDecoder::BlockDecoder(Codec c) : codec_(c) {
   if (c == Codec::kZlib) zlib_ = std::make_unique<Inflater>();
   if (c == Codec::kGzip) zlib_ = std::make_unique<Inflater>(Inflater::Container::kGzip);
+  if (c == Codec::kZstd) zstd_ = std::make_unique<ZstdDecoder>();
 }
 
 void BlockDecoder::feed(const uint8_t* p, size_t n) {
   if (zlib_) return zlib_->feed(p, n);
+  if (zstd_) return zstd_->feed(p, n);
   if (in_pos_ > 0 && in_pos_ == in_.size()) {
     in_.clear();
     in_pos_ = 0;
@@ -136,6 +148,7 @@ bool BlockDecoder::decode_some() {
 
 size_t BlockDecoder::read(uint8_t* dst, size_t cap) {
   if (zlib_) return zlib_->read(dst, cap);
+  if (zstd_) return zstd_->read(dst, cap);
   while (out_pos_ == out_.size()) {
     if (!decode_some()) return 0;
   }

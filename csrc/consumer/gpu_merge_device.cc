@@ -649,7 +649,9 @@ bool ReduceTask::merge_gpu_device(bool probe) {
       pcfg.kv_buf_bytes = kv_buf_size_;
       pcfg.pack_version = delivery_pack_;
       pcfg.piece_bytes = delivery_piece_bytes_;
-      admit(std::max<int64_t>(0, raw + raw / 8 - (int64_t)ws.in.held()), [&](int64_t rb) {
+      // (zstd: what a zlib task takes plus the decoder's literal scratch, 128 KiB a partition)
+      const int64_t lit = dev_inflate && codec_ == Codec::kZstd ? (int64_t)parts.size() * gpu::zstd_literal_scratch() : 0;
+      admit(std::max<int64_t>(0, raw + raw / 8 + lit - (int64_t)ws.in.held()), [&](int64_t rb) {
         return gpu::fixed_round_ws_bytes(std::min(rb, raw), (int)parts.size(), &pcfg);
       });
     }

@@ -40,7 +40,7 @@ struct DeviceMergeOut {
   int64_t records = 0;
   int64_t records_in = 0;      // records merged (== records without a combiner)
   int64_t decoded_blocks = 0;
-  int64_t decoded_streams = 0;  // zlib / gzip partitions inflated on the device (they have no blocks)
+  int64_t decoded_streams = 0;  // zlib / gzip / zstd partitions decoded on the device (they have no blocks)
   // IFile checksum trailers (uda/ifile.h) found on the merge's runs and stripped; of those, verified
   int64_t trailers = 0, checksum_parts = 0, checksum_bytes = 0;
   double checksum_ms = 0;  // the device CRC, from launch to its result being read
@@ -66,7 +66,7 @@ struct DeviceWorkspace {
   gpu::DeviceBuffer fetched;  // device fetch: bytes of the partitions the providers declined as descriptors
   gpu::GenericMerger merger;
   gpu::DeviceBlockDecoder decoder;
-  gpu::DeviceStreamDecoder inflater;  // zlib / gzip partitions: one stream each, no blocks
+  gpu::DeviceStreamDecoder inflater;  // zlib / gzip / zstd partitions: one stream each, no blocks
   gpu::PinnedBuffer ring;          // 2 x kPieceBytes, D2H staging of merged output
   gpu::GenericRoundsWs rounds;     // key-range round planner scratch (device fetch, generic keys)
   gpu::DeviceBuffer frame_scratch, frame_descs; // device framing walk of compressed partitions (device fetch)
@@ -120,7 +120,7 @@ struct DeviceWorkspace {
   int64_t device_bytes() const {
     return (int64_t)(in.held() + out.held() + packed.held() + out2.held() + fetched.held() + frame_scratch.held() +
                      frame_descs.held()) +
-           merger.workspace_bytes() + checksum.device_bytes();
+           merger.workspace_bytes() + checksum.device_bytes() + inflater.scratch_bytes();
   }
 };
 

@@ -329,7 +329,16 @@ int64_t MofFetcher::pull(uint8_t* dst, int64_t cap) {
         tail_decided_ = true;
         dec_->feed(stored_, (size_t)stored_n_);
         (void)read(dst + r, 0);  // (no output is left: this reads the stream's end, or throws)
+        // zstd: the held-back bytes are the end of the frame's last block, not a check word, so that block is
+        // decoded only now and waits in the decoder: the pulls that follow hand it out, and the frame has ended
+        if (codec_ == Codec::kZstd && !dec_->idle() && !dec_->starved()) return (int64_t)r;
         if (!dec_->idle()) throw UdaError("compressed MOF " + p_.map_id + " ended inside its " + codec_name(codec_) + " stream");
+        if (raw_len_ > 0 && decoded_ != raw_len_)
+          throw UdaError("compressed map output " + p_.map_id + " decodes to " + std::to_string(decoded_) +
+                         " bytes, its index says " + std::to_string(raw_len_));
+      } else if (codec_ == Codec::kZstd && tail_decided_ && dec_->idle()) {
+        // these are the last bytes of the deferred block(s) above: the length is held against the index now,
+        // before the consumer sees the EOF marker in them and stops reading
         if (raw_len_ > 0 && decoded_ != raw_len_)
           throw UdaError("compressed map output " + p_.map_id + " decodes to " + std::to_string(decoded_) +
                          " bytes, its index says " + std::to_string(raw_len_));
@@ -347,6 +356,9 @@ int64_t MofFetcher::pull(uint8_t* dst, int64_t cap) {
         continue;
       }
       if (!dec_->idle()) throw UdaError("compressed MOF ended inside a block");
+      if (codec_ == Codec::kZstd && raw_len_ > 0 && decoded_ != raw_len_)  // (a frame without trailer: see above)
+        throw UdaError("compressed map output " + p_.map_id + " decodes to " + std::to_string(decoded_) +
+                       " bytes, its index says " + std::to_string(raw_len_));
       return 0;
     }
     if (tmp_.empty()) tmp_.resize((size_t)buf_size_);
@@ -490,7 +502,7 @@ void ReduceTask::on_init(const InitParams& p_in) {
   if (kind_ == KeyKind::kUnsupported)
     throw ProtocolError("using compare function for unsupported type: " + p.key_class);
   bool unsup = false;
-  codec_ = map_output_codec(p.codec, &unsup);
+  codec_ = job_codec(p.codec, &unsup);
   if (unsup) throw ProtocolError("unsupported compression codec: " + p.codec);
   const int maps = p.num_maps;
   // LPQ geometry (reduce_task::init, reducer.cc:260-285)

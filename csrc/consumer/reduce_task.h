@@ -57,7 +57,7 @@ struct ReduceStats {
   double fetch_ms = 0, merge_ms = 0, total_ms = 0;
   double wait_ms = 0;             // time the merge waited on the network (total_wait_mem_time)
   int64_t device_decoded_blocks = 0;  // compressed blocks decoded in HBM by the F6 kernels
-  int64_t device_decoded_streams = 0;  // zlib / gzip partitions inflated in HBM (no blocks: stays out of the above)
+  int64_t device_decoded_streams = 0;  // zlib / gzip / zstd partitions decoded in HBM (no blocks: stays out of the above)
   int64_t rpq_rounds = 0;             // GPU hybrid: key-range rounds of the RPQ merge; device fetch: merge rounds
   int64_t hybrid_direct = 0;          // GPU hybrid: RPQ rounds straight over the fetched partitions (no LPQ level)
   int64_t merge_budget_from_ledger = 0;  // staged path: input budget capped by the HBM ledger's headroom

@@ -385,6 +385,60 @@ struct InflateGeometry {
 };
 InflateGeometry inflate_geometry();
 
+// ---------------------------------------------------------------- zstd frames, zstd.hip
+// One RFC 8878 frame per descriptor (InflateDesc, the same meaning of its fields), decoded by one wave64: a
+// partition as ZStandardCodec's CompressorStream wrote it. The frame starts at the descriptor's first byte;
+// one frame is decoded and what lies behind it is the host's to judge. lit_scratch: n * zstd_literal_scratch()
+// device bytes, frame i's decoded literals of the block in hand at i * zstd_literal_scratch().
+// consumed: bytes of the input the frame took, its content checksum included; produced: bytes written;
+// has_checksum / check_stored: the frame's Content_Checksum flag and the stored word (not verified here:
+// launch_xxh64 over the output, compared on the host). status: InflateStatus; reason: what was wrong.
+struct ZstdResult {
+  int64_t consumed, produced;
+  uint32_t check_stored;
+  int status;
+  int reason;
+  uint32_t has_checksum;
+};
+enum ZstdReason : int {
+  kZstdFine = 0,
+  kZstdMagic,
+  kZstdReservedBit,
+  kZstdDictionary,
+  kZstdBlockType,
+  kZstdBlockSize,
+  kZstdLiterals,
+  kZstdHuffmanTree,
+  kZstdHuffmanStream,
+  kZstdTreeless,
+  kZstdSequences,
+  kZstdFseTable,
+  kZstdRepeatMode,
+  kZstdBitstream,
+  kZstdSequenceCode,
+  kZstdLiteralsShort,
+  kZstdOffset,
+  kZstdContentSize,
+  kZstdInputEnds,
+  kZstdOutputFull,
+  kZstdBitstreamLeft,
+  kZstdReasons
+};
+const char* zstd_reason_text(int reason);
+void launch_zstd_frames(const uint8_t* in, uint8_t* out, const InflateDesc* d, int n, ZstdResult* r, uint8_t* lit_scratch,
+                        hipStream_t s);
+struct ZstdGeometry {
+  int waves_per_block, lds_per_wave, literal_scratch;
+};
+ZstdGeometry zstd_geometry();
+inline int64_t zstd_literal_scratch() { return 128 * 1024; }
+
+// ---------------------------------------------------------------- XXH64 of device-resident byte ranges
+// XXH64 (seed 0) of n ranges in one launch (xxh64.hip): four lanes per range hold the four accumulators, lane j
+// taking bytes [32 i + 8 j, 32 i + 8 j + 8) of stripe i; then the merge and the tail. ptrs / lens / out: device
+// arrays of n. A zstd frame's content checksum is the low 32 bits.
+void launch_xxh64(const uint8_t* const* ptrs, const int64_t* lens, int n, uint64_t* out, hipStream_t s);
+
 // ---------------------------------------------------------------- Adler-32 of device-resident byte ranges
 // zlib's adler32() of n ranges in one launch (adler32.hip). ptrs / lens / out are device arrays of n; work is
 // 2 * n uint64 of device scratch (zeroed here). A range is summed by several workgroups, whose partial sums

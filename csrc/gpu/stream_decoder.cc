@@ -1,4 +1,4 @@
-// zlib / gzip stream plan and device decode: see stream_decoder.h.
+// zlib / gzip / zstd stream plan and device decode: see stream_decoder.h.
 #include "stream_decoder.h"
 
 #include <cstdio>
@@ -46,6 +46,7 @@ void DeviceStreamDecoder::decode(const StreamPlan& plan, const uint8_t* d_in, ui
                                  const std::vector<std::string>& ids, hipStream_t s, std::vector<int>* tails,
                                  int* failed, std::string* why, Codec container) {
   if (!is_stream_codec(container)) throw UdaError("DeviceStreamDecoder: " + std::string(codec_name(container)) + " is no stream codec");
+  if (container == Codec::kZstd) return decode_zstd(plan, d_in, d_out, ids, s, tails, failed, why);
   const bool gzip = container == Codec::kGzip;
   const int n = (int)plan.descs.size();
   if (failed) *failed = -1;
@@ -135,6 +136,96 @@ void DeviceStreamDecoder::decode(const StreamPlan& plan, const uint8_t* d_in, ui
              std::to_string(r.produced);
     if (tail != 0 && tail != kIFileChecksumBytes)
       return std::string(gzip ? "corrupt gzip stream in map output " : "corrupt zlib stream in map output ") + id + ": " + std::to_string(tail) +
+             " bytes behind its end (an IFile checksum has " + std::to_string(kIFileChecksumBytes) + ")";
+    if (tails) (*tails)[(size_t)i] = (int)tail;
+    return std::string();
+  };
+  for (int i = 0; i < n; ++i) {
+    const std::string err = check(i);
+    if (err.empty()) continue;
+    if (!failed) throw UdaError(err);
+    if (*failed < 0) {
+      *failed = i;
+      if (why) *why = err;
+    }
+  }
+}
+
+void DeviceStreamDecoder::decode_zstd(const StreamPlan& plan, const uint8_t* d_in, uint8_t* d_out,
+                                      const std::vector<std::string>& ids, hipStream_t s, std::vector<int>* tails,
+                                      int* failed, std::string* why) {
+  const int n = (int)plan.descs.size();
+  if (failed) *failed = -1;
+  if (tails) tails->assign((size_t)n, 0);
+  zresults_.assign((size_t)n, ZstdResult{});
+  if (n == 0) return;
+  trace::Range tr("uda.zstd_frames");
+  // scratch: descs | results | xxh ptrs | xxh lens | xxh out | literal scratch (128 KiB a frame)
+  const size_t o_desc = 0, o_res = up16(o_desc + (size_t)n * sizeof(InflateDesc));
+  const size_t o_ptr = up16(o_res + (size_t)n * sizeof(ZstdResult)), o_len = o_ptr + (size_t)n * 8;
+  const size_t o_sum = up16(o_len + (size_t)n * 8), o_lit = up16(o_sum + (size_t)n * 8);
+  const size_t bytes = o_lit + (size_t)n * (size_t)zstd_literal_scratch();
+  if (scratch_.size() < bytes) scratch_.alloc(bytes);  // (exactly: admission reserves 128 KiB a frame, no slack)
+  uint8_t* const base = scratch_.as<uint8_t>();
+  HIP_CHECK(hipMemcpyAsync(base + o_desc, plan.descs.data(), (size_t)n * sizeof(InflateDesc), hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemsetAsync(base + o_res, 0xFF, (size_t)n * sizeof(ZstdResult), s));  // (a status no wave wrote reads as an error)
+  launch_zstd_frames(d_in, d_out, reinterpret_cast<const InflateDesc*>(base + o_desc), n,
+                     reinterpret_cast<ZstdResult*>(base + o_res), base + o_lit, s);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(zresults_.data(), base + o_res, (size_t)n * sizeof(ZstdResult), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  // the content checksum, where a frame carries one: over the bytes just decoded. Only the frames that decoded
+  // and say so are summed (the others get an empty range), and with none there is no launch
+  std::vector<uint64_t> sums((size_t)n, 0);
+  std::vector<const uint8_t*> xptr((size_t)n, nullptr);
+  std::vector<int64_t> xlen((size_t)n, 0);
+  bool any_sum = false;
+  for (int i = 0; i < n; ++i) {
+    const ZstdResult& r = zresults_[(size_t)i];
+    if (r.status != kInflateOk || !r.has_checksum) continue;
+    xptr[(size_t)i] = d_out + plan.descs[(size_t)i].dst;
+    xlen[(size_t)i] = r.produced;  // (<= raw_len: the kernel wrote no further)
+    any_sum = true;
+  }
+  if (any_sum) {
+    HIP_CHECK(hipMemcpyAsync(base + o_ptr, xptr.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(base + o_len, xlen.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+    launch_xxh64(reinterpret_cast<const uint8_t* const*>(base + o_ptr), reinterpret_cast<const int64_t*>(base + o_len), n,
+                 reinterpret_cast<uint64_t*>(base + o_sum), s);
+    HIP_CHECK(hipGetLastError());
+    ++xxh64_launches_;
+    HIP_CHECK(hipMemcpyAsync(sums.data(), base + o_sum, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  auto check = [&](int i) -> std::string {  // "" = frame i is good, its tail filled in
+    const ZstdResult& r = zresults_[(size_t)i];
+    const InflateDesc& d = plan.descs[(size_t)i];
+    const std::string id = (size_t)i < ids.size() ? ids[(size_t)i] : "#" + std::to_string(i);
+    if (r.status != kInflateOk)
+      return "corrupt zstd frame in map output " + id + " (" +
+             (r.status == kInflateTooBig ? "2 GiB or more" : zstd_reason_text(r.reason)) + ", device decode)";
+    const int64_t tail = d.src_len - r.consumed;
+    if (tail >= 4 && tail != kIFileChecksumBytes) {
+      // what the host decoders take for the start of another frame. Asked first: the index's raw length covers
+      // every frame, so the length comparison below would only say that one frame decodes to less
+      uint8_t head[4] = {0, 0, 0, 0};
+      const uint8_t* at = (d_in ? d_in + d.src : reinterpret_cast<const uint8_t*>((uintptr_t)d.src)) + r.consumed;
+      HIP_CHECK(hipMemcpy(head, at, sizeof head, hipMemcpyDefault));
+      const uint32_t magic = (uint32_t)head[0] | ((uint32_t)head[1] << 8) | ((uint32_t)head[2] << 16) | ((uint32_t)head[3] << 24);
+      if (magic == 0xFD2FB528u || (magic & 0xFFFFFFF0u) == 0x184D2A50u)
+        return "zstd map output " + id + " holds more than one frame (the device decode takes one; "
+               "mapred.uda.gpu.decompress=0 decodes it on the host)";
+    }
+    if (r.produced != d.raw_len)
+      return "compressed map output " + id + " decodes to " + std::to_string(r.produced) + " bytes, its index says " +
+             std::to_string(d.raw_len);
+    if (r.has_checksum && r.check_stored != (uint32_t)sums[(size_t)i]) {
+      char buf[64];
+      std::snprintf(buf, sizeof buf, "stored 0x%08x, computed 0x%08x", r.check_stored, (uint32_t)sums[(size_t)i]);
+      return "zstd content checksum mismatch in map output " + id + ": " + buf;
+    }
+    if (tail != 0 && tail != kIFileChecksumBytes)
+      return "corrupt zstd frame in map output " + id + ": " + std::to_string(tail) +
              " bytes behind its end (an IFile checksum has " + std::to_string(kIFileChecksumBytes) + ")";
     if (tails) (*tails)[(size_t)i] = (int)tail;
     return std::string();

@@ -1,4 +1,4 @@
-// Host side of the zlib (DefaultCodec) and gzip (GzipCodec) device decode: one inflate descriptor per partition and the launches
+// Host side of the zlib (DefaultCodec), gzip (GzipCodec) and zstd (ZStandardCodec) device decode: one inflate descriptor per partition and the launches
 // of csrc/gpu/inflate.hip and adler32.hip (gzip: crc32.hip). The sibling of block_decoder.h for the codec that has no blocks:
 // a partition is one zlib stream, its raw size comes from the index and its end (and with it whether an IFile
 // checksum trailer follows) is known only once it has been decoded.
@@ -45,6 +45,13 @@ class DeviceStreamDecoder {
   // stored N, decoded M" (ISIZE against the bytes produced mod 2^32), and, the device inflate decoding one
   // member per stream, "gzip map output <id> holds more than one member (...)" when the bytes behind a good
   // member are neither 0 nor 4 and are 18 or more starting 1f 8b 08. The zlib messages are unchanged.
+  // container = Codec::kZstd: the streams are zstd frames (zstd.hip, one frame per stream). The scratch grows by
+  // zstd_literal_scratch() = 128 KiB per stream for the blocks' decoded literals. XXH64 (xxh64.hip) runs over
+  // the outputs of the frames that carry a content checksum, and is not launched when none does. Errors:
+  // "corrupt zstd frame in map output <id> (<reason>, device decode)" (a dictionary id among the reasons: "needs
+  // a dictionary"), "zstd content checksum mismatch in map output <id>: stored 0x..., computed 0x...", and
+  // "zstd map output <id> holds more than one frame (...)" when the bytes behind a good frame are neither 0 nor
+  // 4 and begin with a frame or skippable-frame magic.
   // failed (optional): instead of throwing, the first stream in error is reported there with its message in
   // *why (-1: none) and the other streams' tails are still filled in. A stream that does not decode has no
   // known end, so the caller that verifies IFile checksums can first hold that partition's bytes against the
@@ -53,8 +60,15 @@ class DeviceStreamDecoder {
               hipStream_t s, std::vector<int>* tails, int* failed = nullptr, std::string* why = nullptr,
               Codec container = Codec::kZlib);
   const std::vector<InflateResult>& results() const { return results_; }
+  const std::vector<ZstdResult>& zstd_results() const { return zresults_; }
+  int64_t scratch_bytes() const { return (int64_t)scratch_.held(); }  // device memory held between decodes
+  int64_t xxh64_launches() const { return xxh64_launches_; }  // launches of the content-checksum kernel so far
 
  private:
+  void decode_zstd(const StreamPlan& plan, const uint8_t* d_in, uint8_t* d_out, const std::vector<std::string>& ids,
+                   hipStream_t s, std::vector<int>* tails, int* failed, std::string* why);
+  std::vector<ZstdResult> zresults_;
+  int64_t xxh64_launches_ = 0;
   DeviceBuffer scratch_;
   std::vector<InflateResult> results_;
 };

@@ -22,10 +22,14 @@ namespace uda {
 // inflate entry points below (and csrc/gpu/inflate.hip) take it. Beyond the reference, like LZ4.
 // kGzip (GzipCodec) is the same deflate data in another wrapper: one RFC 1952 member per partition, checked by
 // a CRC-32 and a length where zlib has an Adler-32. It goes wherever kZlib goes (is_stream_codec).
-enum class Codec { kNone = 0, kSnappy = 1, kLzo = 2, kLz4 = 3, kZlib = 4, kGzip = 5 };
+// kZstd (ZStandardCodec) is a stream codec too, with a format of its own: one RFC 8878 frame per partition
+// (csrc/codec/zstd.cc on the host, csrc/gpu/zstd.hip on the device). It goes wherever kZlib goes too; whoever
+// goes on to decode dispatches three ways (DeviceStreamDecoder::decode, BlockDecoder).
+enum class Codec { kNone = 0, kSnappy = 1, kLzo = 2, kLz4 = 3, kZlib = 4, kGzip = 5, kZstd = 6 };
 
-// The codecs whose partition is one unframed deflate stream (zlib or gzip wrapper), not a sequence of blocks.
-inline bool is_stream_codec(Codec c) { return c == Codec::kZlib || c == Codec::kGzip; }
+// The codecs whose partition is one unframed stream (a zlib stream, a gzip member, a zstd frame), not a sequence
+// of blocks.
+inline bool is_stream_codec(Codec c) { return c == Codec::kZlib || c == Codec::kGzip || c == Codec::kZstd; }
 
 // Map a Hadoop codec class name ("...SnappyCodec", "...LzoCodec", "...Lz4Codec", "...DefaultCodec",
 // "...DeflateCodec") to a codec; kNone for ""/null. Unsupported names (Gzip, BZip2, ZStandard ...) return
@@ -39,6 +43,12 @@ Codec codec_from_class(const std::string& cls, bool* unsupported);
 // codec_from_class's answers are pinned (its callers and tests rely on Gzip being refused there); INIT and
 // every other place that turns the job's codec class into a Codec call this one.
 Codec map_output_codec(const std::string& cls, bool* unsupported);
+// The same for a job, with ZStandardCodec: kZstd for a class name containing "ZStandardCodec", otherwise exactly
+// what map_output_codec answers (whose answers are pinned by tests in turn, ZStandard refused among them). INIT
+// and every other place that turns a job's codec class into a Codec call this one.
+// Three resolvers are debt: each codec added since codec_from_class was pinned has left one behind. Folding them
+// into one is a later change, which is then allowed to touch the tests that pin the two older ones.
+Codec job_codec(const std::string& cls, bool* unsupported);
 const char* codec_name(Codec c);
 
 // ---- Snappy (raw format: varint uncompressed length, then literal/copy tags)
@@ -73,6 +83,67 @@ bool zlib_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, siz
 // CM != 8, a reserved FLG bit, a wrong FHCRC, anything truncated, a CRC-32 or ISIZE that does not match), or
 // more than cap bytes of output.
 bool gzip_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len, size_t* consumed);
+
+// ---- zstd (RFC 8878 frames: what ZStandardCodec's CompressorStream writes, one frame per partition, to our
+// knowledge without dictionary, content size or checksum; the decoder takes everything the format allows).
+// One shot, the contract of gzip_decompress: decodes the frames at src into one output, skipping skippable
+// frames; stops where the bytes that follow cannot start a frame (fewer than 4 bytes, or no frame magic) and says
+// where in *consumed (an IFile checksum behind the last frame is the caller's tail). false: a wrong magic, a
+// reserved descriptor bit or block type, a dictionary id, a block larger than min(window, 128 KiB), a content size
+// or content checksum that does not match, an offset that reaches before the frame's first byte, anything
+// truncated, or more than cap bytes of output. An offset beyond Window_Size but inside the frame's output is
+// taken, as libzstd's one-shot ZSTD_decompress takes it.
+struct ZstdStats {  // what a decode met (coverage counters of the tests)
+  int64_t frames = 0, skippable = 0, max_frame_blocks = 0;
+  int64_t blocks[3] = {0, 0, 0};    // Raw, RLE, Compressed
+  int64_t literals[4] = {0, 0, 0, 0};  // Raw, RLE, Compressed, Treeless
+  int64_t huf_streams[2] = {0, 0};  // sections of 1 stream, of 4 streams
+  int64_t weights[2] = {0, 0};      // direct, FSE-compressed
+  int64_t modes[3][4] = {};         // [LL, OF, ML][Predefined, RLE, FSE_Compressed, Repeat]
+  int64_t sequences = 0, max_offset = 0, checksums = 0;
+};
+bool zstd_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len, size_t* consumed,
+                     ZstdStats* stats = nullptr, std::string* why = nullptr);
+// A small encoder, so that writers and tests can make zstd partitions with no zstd library: one frame, no
+// checksum, no content size, blocks of at most 128 KiB; a greedy hash-chain matcher; compressed blocks with Raw
+// literals and Predefined-mode sequences, an RLE block for a block of one repeated byte, a Raw block where
+// the compressed form is not smaller.
+size_t zstd_max_compressed_length(size_t n);
+size_t zstd_compress(const uint8_t* src, size_t n, uint8_t* dst);
+
+// Incremental zstd decoder: feed / read / finished / idle / starved / consumed as Inflater below. It restarts at
+// unit boundaries: a frame header, a block header with its whole block, and a 4-byte content checksum are each
+// committed only once whole, whatever the feed granularity. Memory is the frame's Window_Size plus one block (at
+// most 128 KiB) of history and output, and one block of input, however long the frame is; a Window_Size above
+// 128 MiB is refused by name. An offset beyond Window_Size is refused here, wherever the buffer stands (the
+// one-shot decoder, which has the whole output, takes it as libzstd's one-shot call does).
+class ZstdDecoder {
+ public:
+  ZstdDecoder();
+  ~ZstdDecoder();
+  void feed(const uint8_t* p, size_t n);
+  size_t read(uint8_t* dst, size_t cap);  // throws UdaError("corrupt zstd frame: ...")
+  bool finished() const { return state_ == kDone && skip_ == 0; }  // the last frame ended (a skippable one: all skipped)
+  bool idle() const { return finished() && rpos_ == wpos_ && ipos_ == in_.size(); }
+  bool starved() const { return !finished() && rpos_ == wpos_; }
+  uint64_t consumed() const { return dropped_ + ipos_; }
+  size_t history_bytes() const { return buf_.capacity(); }  // memory held for history and output (tests)
+  size_t input_bytes() const { return in_.capacity(); }     // memory held for input not yet decoded (tests)
+
+ private:
+  enum State { kFrame, kBlock, kChecksum, kDone };
+  struct Tables;
+  bool run();
+  std::unique_ptr<Tables> t_;
+  std::vector<uint8_t> in_;
+  size_t ipos_ = 0;
+  uint64_t dropped_ = 0;
+  std::vector<uint8_t> buf_;  // history + output: [0, wpos_) decoded, [rpos_, wpos_) not yet read
+  size_t wpos_ = 0, rpos_ = 0, fstart_ = 0;  // fstart_: where the frame's output begins in buf_ (0 once slid away)
+  uint64_t window_ = 0, frame_out_ = 0, fcs_ = 0, skip_ = 0;  // skip_: bytes of a skippable frame still to drop
+  bool has_fcs_ = false, has_sum_ = false, any_frame_ = false;
+  State state_ = kFrame;
+};
 
 // Incremental: feed compressed bytes in arbitrary pieces, read raw. Memory is a 32 KiB history plus a
 // fixed output buffer however long the stream is. The decoder restarts at unit boundaries: it commits its
@@ -138,17 +209,19 @@ class BlockDecoder {
   // ended, with no input behind it).
   bool idle() const {
     if (zlib_) return zlib_->idle();
+    if (zstd_) return zstd_->idle();
     return out_pos_ == out_.size() && in_.size() == in_pos_ && block_remaining_ == 0;
   }
-  // kZlib / kGzip only: every decoded byte was read and the stream has not ended, so it waits for input (a block
+  // kZlib / kGzip / kZstd only: every decoded byte was read and the stream has not ended, so it waits for input (a block
   // codec's blocks end where their framing says, and this is always false).
-  bool starved() const { return zlib_ && zlib_->starved(); }
+  bool starved() const { return zlib_ ? zlib_->starved() : zstd_ && zstd_->starved(); }
   int64_t blocks() const { return blocks_; }
 
  private:
   bool decode_some();
   Codec codec_;
   std::unique_ptr<Inflater> zlib_;  // kZlib / kGzip: feed / read / idle go to it
+  std::unique_ptr<ZstdDecoder> zstd_;  // kZstd: the same
   std::vector<uint8_t> in_;
   size_t in_pos_ = 0;
   std::vector<uint8_t> out_;

@@ -843,6 +843,80 @@ PYBIND11_MODULE(_uda_native, m) {
     int v = (int)map_output_codec(c, &unsup);
     return unsup ? -1 : v;
   });
+  // What INIT calls: map_output_codec's answers plus ZStandardCodec -> 6. -1 = unsupported.
+  m.def("job_codec", [](const std::string& c) {
+    bool unsup = false;
+    int v = (int)job_codec(c, &unsup);
+    return unsup ? -1 : v;
+  });
+  // zstd (ZStandardCodec): the in-tree encoder (one frame, Raw literals, Predefined-mode sequences) and the
+  // one-shot host decode of one or more frames: (raw bytes, bytes of the input the frames took). ValueError
+  // with the decoder's reason for anything it refuses or more than cap bytes of output.
+  m.def("zstd_compress", [](py::bytes b) {
+    std::string s = b;
+    std::string out(zstd_max_compressed_length(s.size()), '\0');
+    out.resize(zstd_compress((const uint8_t*)s.data(), s.size(), (uint8_t*)&out[0]));
+    return py::bytes(out);
+  });
+  m.def("zstd_decompress", [](py::bytes b, size_t cap) {
+    std::string s = b;
+    std::string out(cap, '\0'), why;
+    size_t n = 0, used = 0;
+    if (!zstd_decompress((const uint8_t*)s.data(), s.size(), (uint8_t*)&out[0], cap, &n, &used, nullptr, &why))
+      throw py::value_error(why);
+    out.resize(n);
+    return py::make_tuple(py::bytes(out), used);
+  }, py::arg("data"), py::arg("cap"));
+  // What a decode of `stream` meets: block types, literal types (1 and 4 streams), weight encodings, each
+  // sequence mode per table. Coverage counters for the tests. ValueError if the stream does not decode into cap bytes.
+  m.def("zstd_decoder_stats", [](py::bytes b, size_t cap) {
+    std::string s = b;
+    std::string out(cap, '\0'), why;
+    size_t n = 0, used = 0;
+    ZstdStats st;
+    if (!zstd_decompress((const uint8_t*)s.data(), s.size(), (uint8_t*)&out[0], cap, &n, &used, &st, &why))
+      throw py::value_error(why);
+    py::dict d;
+    d["frames"] = st.frames;
+    d["skippable"] = st.skippable;
+    d["max_frame_blocks"] = st.max_frame_blocks;
+    d["blocks"] = py::dict(py::arg("raw") = st.blocks[0], py::arg("rle") = st.blocks[1], py::arg("compressed") = st.blocks[2]);
+    d["literals"] = py::dict(py::arg("raw") = st.literals[0], py::arg("rle") = st.literals[1],
+                             py::arg("compressed") = st.literals[2], py::arg("treeless") = st.literals[3],
+                             py::arg("streams1") = st.huf_streams[0], py::arg("streams4") = st.huf_streams[1]);
+    d["weights"] = py::dict(py::arg("direct") = st.weights[0], py::arg("fse") = st.weights[1]);
+    const char* tables[3] = {"ll", "of", "ml"};
+    py::dict modes;
+    for (int t = 0; t < 3; ++t)
+      modes[tables[t]] = py::dict(py::arg("predefined") = st.modes[t][0], py::arg("rle") = st.modes[t][1],
+                                  py::arg("fse") = st.modes[t][2], py::arg("repeat") = st.modes[t][3]);
+    d["modes"] = modes;
+    d["sequences"] = st.sequences;
+    d["max_offset"] = st.max_offset;
+    d["checksums"] = st.checksums;
+    return d;
+  }, py::arg("stream"), py::arg("cap") = (size_t)4 << 20);
+  // The incremental decoder fed in pieces of `piece` bytes, read dry after every feed: (raw, consumed, finished,
+  // the most bytes its history / output buffer held, the most its input buffer held). UdaError text as ValueError.
+  m.def("zstd_stream_decode", [](py::bytes b, size_t piece) {
+    std::string s = b;
+    if (piece == 0) throw py::value_error("piece == 0");
+    ZstdDecoder d;
+    std::string out;
+    std::vector<uint8_t> tmp(1 << 16);
+    size_t most = 0, most_in = 0;
+    try {
+      for (size_t off = 0; off < s.size(); off += piece) {
+        d.feed((const uint8_t*)s.data() + off, std::min(piece, s.size() - off));
+        for (size_t k; (k = d.read(tmp.data(), tmp.size())) > 0;) out.append((const char*)tmp.data(), k);
+        most = std::max(most, d.history_bytes());
+        most_in = std::max(most_in, d.input_bytes());
+      }
+    } catch (const UdaError& e) {
+      throw py::value_error(e.what());
+    }
+    return py::make_tuple(py::bytes(out), d.consumed(), d.finished(), most, most_in);
+  }, py::arg("stream"), py::arg("piece"));
   m.def("block_compress", [](int codec, py::bytes b, size_t block) {
     std::string s = b;
     auto v = block_compress((Codec)codec, (const uint8_t*)s.data(), s.size(), block);
@@ -2639,6 +2713,115 @@ PYBIND11_MODULE(_uda_native, m) {
     for (auto& o : outs) l.append(py::bytes(o));
     return py::make_tuple(py::object(l), consumed, ms);
   }, py::arg("streams"), py::arg("raw_lens"), py::arg("device") = 0, py::arg("container") = "zlib");
+  // zstd frames decoded on the device in one launch (gpu/zstd.hip), laid out as gpu_inflate_streams lays its
+  // streams: 256 guard bytes of 0xA5 behind every output, checked before anything is returned or raised.
+  // Returns (outputs, consumed, frames that carried a content checksum, ms, launches of the XXH64 kernel).
+  m.def("gpu_zstd_streams", [](const std::vector<std::string>& streams, const std::vector<int64_t>& raw_lens, int device) {
+    if (streams.size() != raw_lens.size()) throw py::value_error("one raw length per stream");
+    constexpr int64_t kGuard = 256;
+    std::vector<std::string> outs;
+    std::vector<int64_t> consumed;
+    int64_t with_sum = 0, xxh_launches = 0;
+    double ms = 0;
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      gpu::StreamPlan plan;
+      plan.raw_offset.assign(1, 0);
+      int64_t staged = 0, out_bytes = 0;
+      for (size_t i = 0; i < streams.size(); ++i) {
+        if (raw_lens[i] < 0) throw UdaError("raw length < 0");
+        plan.descs.push_back(gpu::InflateDesc{staged, (int64_t)streams[i].size(), out_bytes, raw_lens[i]});
+        staged += (int64_t)streams[i].size();
+        out_bytes += raw_lens[i] + kGuard;
+        plan.raw_offset.push_back(out_bytes);
+      }
+      plan.raw_total = out_bytes;
+      gpu::DeviceBuffer din((size_t)std::max<int64_t>(staged, 16)), dout((size_t)std::max<int64_t>(out_bytes, 16));
+      hipStream_t s;
+      HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      for (size_t i = 0; i < streams.size(); ++i)
+        if (!streams[i].empty())
+          HIP_CHECK(hipMemcpyAsync(din.as<uint8_t>() + plan.descs[i].src, streams[i].data(), streams[i].size(),
+                                   hipMemcpyHostToDevice, s));
+      if (out_bytes) HIP_CHECK(hipMemsetAsync(dout.as(), 0xA5, (size_t)out_bytes, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      gpu::DeviceStreamDecoder dec;
+      std::string err;
+      auto t0 = std::chrono::steady_clock::now();
+      try {
+        dec.decode(plan, din.as<uint8_t>(), dout.as<uint8_t>(), {}, s, nullptr, nullptr, nullptr, Codec::kZstd);
+      } catch (const UdaError& e) {
+        err = e.what();
+      }
+      ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      std::string all((size_t)out_bytes, '\0');
+      if (out_bytes) HIP_CHECK(hipMemcpyAsync(&all[0], dout.as(), all.size(), hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      HIP_CHECK(hipStreamDestroy(s));
+      for (size_t i = 0; i < streams.size(); ++i) {
+        const size_t g0 = (size_t)(plan.descs[i].dst + raw_lens[i]);
+        for (size_t k = 0; k < (size_t)kGuard; ++k)
+          if ((uint8_t)all[g0 + k] != 0xA5)
+            throw UdaError("device zstd decode wrote past the output of stream " + std::to_string(i) + " (guard byte " +
+                           std::to_string(k) + ")");
+      }
+      if (!err.empty()) throw UdaError(err);
+      for (size_t i = 0; i < streams.size(); ++i) {
+        outs.push_back(all.substr((size_t)plan.descs[i].dst, (size_t)raw_lens[i]));
+        consumed.push_back(dec.zstd_results()[i].consumed);
+        with_sum += dec.zstd_results()[i].has_checksum ? 1 : 0;
+      }
+      xxh_launches = dec.xxh64_launches();
+    }
+    py::list l;
+    for (auto& o : outs) l.append(py::bytes(o));
+    return py::make_tuple(py::object(l), consumed, with_sum, ms, xxh_launches);
+  }, py::arg("streams"), py::arg("raw_lens"), py::arg("device") = 0);
+  m.def("gpu_zstd_geometry", [] {
+    const gpu::ZstdGeometry g = gpu::zstd_geometry();
+    py::dict d;
+    d["waves_per_block"] = g.waves_per_block;
+    d["lds_per_wave"] = g.lds_per_wave;
+    d["literal_scratch"] = g.literal_scratch;
+    return d;
+  });
+  // XXH64 (seed 0) of every buffer in one launch (gpu/xxh64.hip).
+  m.def("gpu_xxh64", [](const std::vector<std::string>& buffers, int device) {
+    std::vector<uint64_t> out(buffers.size());
+    {
+      py::gil_scoped_release rel;
+      HIP_CHECK(hipSetDevice(device));
+      const int n = (int)buffers.size();
+      if (n == 0) return out;
+      std::vector<int64_t> offs, lens;
+      int64_t total = 16;
+      for (auto& b : buffers) {
+        offs.push_back(total);
+        lens.push_back((int64_t)b.size());
+        total += (int64_t)b.size();
+      }
+      gpu::DeviceBuffer data((size_t)total), meta((size_t)n * 24);
+      std::vector<const uint8_t*> ptrs;
+      for (int i = 0; i < n; ++i) ptrs.push_back(data.as<uint8_t>() + offs[(size_t)i]);
+      hipStream_t s;
+      HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+      for (int i = 0; i < n; ++i)
+        if (!buffers[(size_t)i].empty())
+          HIP_CHECK(hipMemcpyAsync(data.as<uint8_t>() + offs[(size_t)i], buffers[(size_t)i].data(), buffers[(size_t)i].size(),
+                                   hipMemcpyHostToDevice, s));
+      uint8_t* const mb = meta.as<uint8_t>();
+      HIP_CHECK(hipMemcpyAsync(mb, ptrs.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+      HIP_CHECK(hipMemcpyAsync(mb + (size_t)n * 8, lens.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
+      gpu::launch_xxh64(reinterpret_cast<const uint8_t* const*>(mb), reinterpret_cast<const int64_t*>(mb + (size_t)n * 8), n,
+                        reinterpret_cast<uint64_t*>(mb + (size_t)n * 16), s);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipMemcpyAsync(out.data(), mb + (size_t)n * 16, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      HIP_CHECK(hipStreamDestroy(s));
+    }
+    return out;
+  }, py::arg("buffers"), py::arg("device") = 0);
   // zlib.adler32 of every item in one batched launch (gpu/adler32.hip); item i starts `misalign` bytes past a
   // 16-byte boundary of the device buffer.
   // timed: returns (values, ms of the launch alone, from its queueing to its result) instead.

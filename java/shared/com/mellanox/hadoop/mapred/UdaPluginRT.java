@@ -73,7 +73,7 @@ class UdaPluginRT extends UdaPlugin implements UdaCallable {
     p.add(Long.toString(maxBufKb * 1024));
     p.add(Long.toString(minBufKb * 1024));
     p.add(conf.getMapOutputKeyClass().getName());
-    // the class name goes through unchanged (the native side maps it, codec_from_class). A job that only turns
+    // the class name goes through unchanged (the native side maps it, job_codec: ZStandardCodec among them). A job that only turns
     // compression on has no codec key: Hadoop then writes with DefaultCodec
     // (JobConf.getMapOutputCompressorClass(DefaultCodec.class)), so that is the name to send, not "null"
     String codec = conf.getCompressMapOutput()

@@ -2,7 +2,7 @@
 
 file.out holds one IFile partition per reducer back to back (optionally block-compressed, or with
 codec "zlib" each partition one zlib stream with no framing, as DefaultCodec's CompressorStream writes it, or
-with codec "gzip" one gzip member, as GzipCodec's does);
+with codec "gzip" one gzip member, as GzipCodec's does, or with codec "zstd" one zstd frame, as ZStandardCodec's);
 file.out.index holds, per partition, three big-endian longs {startOffset, rawLength, partLength}
 followed by a CRC32 of those bytes as a big-endian long (Hadoop SpillRecord). The index record is
 the tuple the provider's getPathUda callback returns (IndexRecordBridge.java:26-34).
@@ -16,7 +16,7 @@ import zlib
 
 from .._native import native
 
-CODECS = {None: 0, "snappy": 1, "lzo": 2, "lz4": 3, "zlib": 4, "gzip": 5}
+CODECS = {None: 0, "snappy": 1, "lzo": 2, "lz4": 3, "zlib": 4, "gzip": 5, "zstd": 6}
 CODEC_CLASSES = {
     None: None,
     "snappy": "org.apache.hadoop.io.compress.SnappyCodec",
@@ -24,6 +24,7 @@ CODEC_CLASSES = {
     "lz4": "org.apache.hadoop.io.compress.Lz4Codec",
     "zlib": "org.apache.hadoop.io.compress.DefaultCodec",
     "gzip": "org.apache.hadoop.io.compress.GzipCodec",
+    "zstd": "org.apache.hadoop.io.compress.ZStandardCodec",
 }
 
 
@@ -41,6 +42,8 @@ def encode_partitions(partitions: list[bytes], codec: str | None = None, block_s
             body = zlib.compress(p)
         elif codec == "gzip":  # one member with the bare header, what Hadoop's writers emit
             body = gzip.compress(p, mtime=0)
+        elif codec == "zstd":  # one frame from the in-tree encoder (no zstd library is needed)
+            body = native().zstd_compress(p)
         else:
             body = native().block_compress(CODECS[codec], p, block_size) if codec else p
         if checksum:
